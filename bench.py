@@ -24,7 +24,9 @@ forward / mean forward duration, against the dense bf16 MFMA peak (2.5 PF).
 traffic: HBM bytes per forward from a rocprofv3 --pmc pass (profiles/traffic_*.json,
 FETCH_SIZE x2 + WRITE_SIZE per the MI355X guide), else null.
 cpu_baseline: the oracle (PyTorch-CPU fp32 restatement + C NMS) on a bounded
-sample, rank 0 only.
+sample, rank 0 only; measured with --full only (a plain run does what the headline figure
+needs: set-up, warm-up, the timed steps, the result line).
+--dump-outputs DIR: what the last timed step returned, as float32 DIR/<name>.npy (rank 0).
 """
 from __future__ import annotations
 
@@ -90,8 +92,14 @@ def parse():
                          "the reference's precision without --fp16)")
     ap.add_argument("--conf", type=float, default=0.5)
     ap.add_argument("--nms", type=float, default=0.65)
-    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="budget of the CPU baseline sample")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the cpu_baseline leg (a plain run "
+                         "sets up, warms up, times the steps and prints the result line)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy "
+                         "(float32; rank 0)")
+    ap.add_argument("--cpu-seconds", type=float, default=15.0, help="with --full: budget of the CPU baseline sample")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
     ap.add_argument("--fwd-priority", action="store_true",
                     help="run the forward on a high-priority stream (the NMS side stream stays normal)")
     ap.add_argument("--two-slot", action="store_true",
@@ -116,6 +124,8 @@ def parse():
     ap.add_argument("--workload", default="infer", choices=["infer", "train"],
                     help="infer: BASELINE configs[1] (default); train: configs[2] train step (8 images / GPU)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.workload == "train" and args.batch == 32:
         args.batch = 8  # -b 64 over -d 8 (config.py:249-250)
     if args.dtype is None:
@@ -199,6 +209,23 @@ def load_traffic(model, batch, size, dtype, workload="infer"):
                 (workload, model, batch, size, dtype):
             best = d
     return best
+
+
+DUMP_ELEMS = 4 << 20  # --dump-outputs: most elements written of one array (16 MiB as float32)
+
+
+def sample_index(n: int, keep: int) -> np.ndarray:
+    """--dump-outputs: the same sorted `keep` of n indices in every run (all n if they fit)."""
+    if n <= keep:
+        return np.arange(n)
+    return np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: one float32 DIR/<name>.npy per array."""
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
 
 
 def layer_table(plan, iters=5):
@@ -379,6 +406,14 @@ def main_train(args, world, rank):
     dt_max = max_over_ranks(dt, world)
     gpu_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
     loss = float(out["total_loss"].detach())
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back (its losses) and left behind (a fixed sample of the weights)
+        arrays = {k: np.asarray(float(v.detach()) if torch.is_tensor(v) else float(v)) for k, v in out.items()
+                  if (torch.is_tensor(v) and v.numel() == 1) or isinstance(v, (int, float))}
+        flat = torch.cat([p.detach().reshape(-1).float() for p in model.parameters()])
+        keep = sample_index(flat.numel(), DUMP_ELEMS)
+        arrays["parameters_sample"] = flat[torch.from_numpy(keep).to(dev)].cpu().numpy()
+        dump_outputs(args.dump_outputs, arrays)
     from yolox_amd import train as _T
     if _T._LAUNCH_LOG is not None and rank == 0:  # diagnostic: conv / wgrad launches of every step
         with open(os.environ["YOLOX_AMD_TRAIN_LOG"], "w") as f:
@@ -423,7 +458,7 @@ def main_train(args, world, rank):
         **({"traffic_source": ttr.get("source")} if ttr is not None else {}),
         "host_issue_ms_per_step": round(host_s / args.steps * 1e3, 3),
     }
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         result["cpu_baseline"] = cpu_baseline_train(args, args.cpu_seconds)
     else:
         result["cpu_baseline"] = None
@@ -522,10 +557,10 @@ def main():
     filt = [torch.cuda.Event() for _ in range(2)]
     fwd_done = torch.cuda.Event()
     state = {"k": 0}
-    det, counts = dets[0], cnts[0]
+    det, counts, out = dets[0], cnts[0], None
 
     def step(ev0=None, ev1=None):
-        nonlocal det, counts
+        nonlocal det, counts, out
         k = state["k"]
         if not args.serial_nms and k >= slots:
             stream.wait_event(filt[(k - slots) % 2])  # the filter of the last batch in this output slot
@@ -569,6 +604,17 @@ def main():
     dt_max = max_over_ranks(dt, world)
     fwd_ms = float(np.mean([a.elapsed_time(b) for a, b in evs]))
     n_det = counts.cpu().tolist()
+    if args.dump_outputs and rank == 0:
+        # what the last timed step handed back: its detections (rows [x1 y1 x2 y2 obj cls_conf cls], the rows
+        # past an image's count zeroed -- the NMS leaves them unwritten), the counts, and a fixed sample of
+        # anchors of the prediction it filtered (the forward's rows, boxes xyxy after the NMS filter)
+        d = det.cpu().numpy()[:, :max(1, DUMP_ELEMS // (B * 7))].copy()
+        d[np.arange(d.shape[1])[None, :] >= np.asarray(n_det)[:, None]] = 0.0
+        keep = sample_index(A, max(1, DUMP_ELEMS // (B * out.shape[2])))
+        dump_outputs(args.dump_outputs, {
+            "detections": d, "counts": np.asarray(n_det),
+            "prediction_sample": out[:, torch.from_numpy(keep).to(dev)].cpu().numpy(),
+            "prediction_sample_anchors": keep})
 
     if rank != 0:
         if world > 1:
@@ -625,7 +671,7 @@ def main():
     }
     if traffic is not None:
         result["roofline"]["traffic_source"] = traffic.get("source")
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         result["cpu_baseline"] = cpu_baseline(args, args.cpu_seconds)
     else:
         result["cpu_baseline"] = None

@@ -23,6 +23,8 @@ Outputs (all under tests/golden/ unless stated):
   simota_640.npz         get_assignments on synthetic 640 predictions, G=50
   boxes.npz              bboxes_iou (xyxy / cxcywh), IouLoss
   postprocess_pre_nms.npz  the (boxes, scores, idxs) the reference gives batched_nms
+  cocoeval.npz           the reference's compiled COCO evaluator (oracle/_ref) on the synthetic
+                         cases of tests/test_coco_map.py (`make_golden.py cocoeval`)
 """
 from __future__ import annotations
 
@@ -594,6 +596,21 @@ def gen_resize(ref) -> None:
         arrays[f"{size[0]}x{size[1]}.image"] = y.numpy()
         arrays[f"{size[0]}x{size[1]}.targets"] = t2.numpy()
     save("resize_preprocess.npz", **arrays)
+
+
+def gen_cocoeval(ref) -> None:
+    """precision / recall / scores of the reference's compiled COCO evaluator (oracle/_ref,
+    `make -C oracle ref`) on the synthetic cases of tests/test_coco_map.py."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import test_coco_map as T
+    mod = T.ref_module()
+    if mod is None:
+        sys.exit("oracle/_ref/fast_cocoeval not built: make -C oracle ref")
+    arrays = {}
+    for case in T.CASES:
+        res = T.reference_eval(mod, *T.case_inputs(case))
+        arrays.update({f"{case}_{k}": res[k] for k in T.KEYS})
+    save("cocoeval.npz", **arrays)
 
 
 def main() -> None:

@@ -38,6 +38,23 @@ def test_single_gpu_default_is_configs_1():
         assert out["metric"] == json.load(f)["metric"]
 
 
+def test_dump_outputs_files(tmp_path):
+    """--dump-outputs: float32 <name>.npy files, and the same sample of a large output in every run."""
+    import numpy as np
+
+    import bench
+    keep = bench.sample_index(10000, 100)
+    assert keep.shape == (100,) and np.all(np.diff(keep) > 0) and 0 <= keep[0] and keep[-1] < 10000
+    assert np.array_equal(keep, bench.sample_index(10000, 100))
+    assert np.array_equal(bench.sample_index(7, 100), np.arange(7))
+    d = str(tmp_path / "dump")
+    bench.dump_outputs(d, {"counts": np.array([3, 5], dtype=np.int32), "loss": np.asarray(1.5)})
+    assert sorted(os.listdir(d)) == ["counts.npy", "loss.npy"]
+    c = np.load(os.path.join(d, "counts.npy"))
+    assert c.dtype == np.float32 and c.tolist() == [3.0, 5.0]
+    assert np.load(os.path.join(d, "loss.npy")).dtype == np.float32
+
+
 def test_metric_labels_name_the_config():
     assert "configs[3]" in run_bench("--dry-run", "--model", "yolox_l", "--dtype", "fp16", "--batch", "16")["metric"]
     m = run_bench("--dry-run", "--workload", "train")["metric"]

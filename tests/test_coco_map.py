@@ -3,8 +3,11 @@ evaluator: yolox/layers/cocoeval/cocoeval.cpp compiled from the reference by
 `make -C oracle ref` (oracle/_ref, build container only) and driven exactly as
 CocoEvalOpt (fast_coco_eval_api.py:24-149) drives it.  pycocotools is absent; its
 computeIoU / _prepare / loadRes steps are restated on the test side (numpy) to feed the
-reference module.  Bar: identical precision / recall / scores arrays (bit for bit) and
-summary stats; plus known answers that need no reference."""
+reference module.  Its arrays for the cases below are recorded in tests/golden/cocoeval.npz
+(`make_golden.py cocoeval`), so the comparison runs from the repository alone; where
+oracle/_ref is built, the record is also held against the module itself.  Bar: identical
+precision / recall / scores arrays (bit for bit) and summary stats; plus known answers
+that need no reference."""
 import glob
 import importlib.util
 import os
@@ -16,15 +19,31 @@ import pytest
 from conftest import REPO
 
 REF_SO = glob.glob(os.path.join(REPO, "oracle", "_ref", "fast_cocoeval*.so"))
+KEYS = ("precision", "recall", "scores")
 
 
 def ref_module():
+    """The compiled reference evaluator, or None where oracle/_ref is not built."""
     if not REF_SO:
-        pytest.skip("oracle/_ref/fast_cocoeval not built (needs /root/reference: make -C oracle ref)")
+        return None
     spec = importlib.util.spec_from_file_location("fast_cocoeval", REF_SO[0])
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
     return mod
+
+
+def reference_result(golden, case, gt, dets, p):
+    """The reference evaluator's arrays for ``case``: as recorded from it in
+    tests/golden/cocoeval.npz (make_golden.py cocoeval), so the comparison needs no compiled
+    reference; where oracle/_ref is built the record must also equal what it computes now."""
+    rec = golden("cocoeval.npz")
+    ref = {k: rec[f"{case}_{k}"] for k in KEYS}
+    mod = ref_module()
+    if mod is not None:
+        live = reference_eval(mod, gt, dets, p)
+        for k in KEYS:
+            np.testing.assert_array_equal(ref[k], live[k], err_msg=f"recorded {k} vs compiled reference")
+    return ref
 
 
 def synthetic(seed, n_img=10, cats=(1, 3, 7, 8, 20), dets_per_img=140):
@@ -105,30 +124,39 @@ def reference_eval(mod, gt, dets, p):
             "scores": np.array(ev["scores"]).reshape(counts)}
 
 
+CASES = ("seed0", "seed1", "seed2", "other_settings")  # the cases recorded in tests/golden/cocoeval.npz
+
+
+def case_inputs(case):
+    """(gt, dets, params) of a recorded case."""
+    from yolox_amd.evaluators import COCOParams
+    if case == "other_settings":
+        gt, dets = synthetic(5, n_img=6, dets_per_img=60)
+        return gt, dets, COCOParams(iouThrs=np.array([0.3, 0.5]), maxDets=[5, 20, 50])
+    gt, dets = synthetic(int(case[len("seed"):]))
+    return gt, dets, COCOParams()
+
+
 @pytest.mark.parametrize("seed", [0, 1, 2])
-def test_bbox_eval_identical_to_reference_cocoeval(seed):
-    from yolox_amd.evaluators import COCOParams, coco_bbox_eval, summarize
-    mod = ref_module()
-    gt, dets = synthetic(seed)
-    p = COCOParams()
+def test_bbox_eval_identical_to_reference_cocoeval(seed, golden):
+    from yolox_amd.evaluators import coco_bbox_eval, summarize
+    gt, dets, p = case_inputs(f"seed{seed}")
     ours = coco_bbox_eval(gt, dets, p)
-    ref = reference_eval(mod, gt, dets, p)
-    for k in ("precision", "recall", "scores"):
+    ref = reference_result(golden, f"seed{seed}", gt, dets, p)
+    for k in KEYS:
         assert ours[k].shape == ref[k].shape
         np.testing.assert_array_equal(ours[k], ref[k], err_msg=k)
     np.testing.assert_array_equal(ours["stats"], summarize(ref, p))
     assert 0.0 < ours["stats"][0] < 1.0
 
 
-def test_bbox_eval_other_settings_identical_to_reference():
+def test_bbox_eval_other_settings_identical_to_reference(golden):
     """Non-default max-dets (cut below the per-image detection count) and two IoU thresholds."""
-    from yolox_amd.evaluators import COCOParams, coco_bbox_eval
-    mod = ref_module()
-    gt, dets = synthetic(5, n_img=6, dets_per_img=60)
-    p = COCOParams(iouThrs=np.array([0.3, 0.5]), maxDets=[5, 20, 50])
+    from yolox_amd.evaluators import coco_bbox_eval
+    gt, dets, p = case_inputs("other_settings")
     ours = coco_bbox_eval(gt, dets, p)
-    ref = reference_eval(mod, gt, dets, p)
-    for k in ("precision", "recall", "scores"):
+    ref = reference_result(golden, "other_settings", gt, dets, p)
+    for k in KEYS:
         np.testing.assert_array_equal(ours[k], ref[k], err_msg=k)
 
 
