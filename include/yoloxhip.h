@@ -589,8 +589,15 @@ typedef struct {
  * train = 1: obj/cls stay logits (get_output_and_grid, :213-231); train = 2 (ABI 16): the
  * eval rows without the box decode (decode_in_inference = False, :208-211): reg raw, obj/cls
  * sigmoid.
- * scores (ABI 18, NULL = none; eval decode rows (train = 0) of the 64 / 128 / 256-channel 16-bit levels
- * only): per anchor 8 floats {obj * max class, max class, its index, obj, cx, cy, w, h} -- the fp32
+ * Built for the 16-bit dtypes, 1 <= num_classes <= 80 and cin 64 / 96 / 128 / 192 / 256 / 320 (the six
+ * presets' head widths): one kernel per (dtype, cin, ceil(num_classes / 16) class fragments, train).
+ * Anything else is YXH_EUNSUPPORTED -- more than 80 classes too: the weights of more than 5 class
+ * fragments do not fit in a wave's registers, and the caller runs the two 1x1 pred convs instead.  cin 96 /
+ * 192 / 320 need feature rows that are 16-byte aligned (pointer, cstride, bstride); the tile kernel
+ * behind YXH_HEAD_V1=1 is built for cin 64 / 128 / 256 only.  The first 5 + C columns of a C-class launch
+ * equal, bit for bit, those of a launch with more classes whose w_cls / b_cls start with the same C rows.
+ * scores (ABI 18, NULL = none; eval decode rows (train = 0) of 16-byte aligned 16-bit levels of the widths
+ * above only): per anchor 8 floats {obj * max class, max class, its index, obj, cx, cy, w, h} -- the fp32
  * values utils.postprocess's filter computes from the row (boxes.py:46-48: first maximum, obj *
  * conf) and the row's box, from the same registers -- at [image][a_off + pixel], image stride
  * out_bstride / (5 + C) anchors.  yxh_postprocess_scored reads these 32 bytes instead of the row. */

@@ -119,11 +119,17 @@ _CSP_FUSION = os.environ.get("YOLOX_AMD_CSP_FUSION", "1") != "0"
 _HEAD_FUSION = {int(v) for v in os.environ.get("YOLOX_AMD_HEAD_FUSION", "").split(",") if v.strip()}
 # fragment-major weight copies for the weight-stationary tiles (YOLOX_AMD_WFRAG=0: row layout only)
 _WFRAG = os.environ.get("YOLOX_AMD_WFRAG", "1") != "0"
+# a head level's three preds + cat + sigmoid + decode as one head_pred launch (YOLOX_AMD_HEAD_PRED=0: the two
+# 1x1 pred convs with the fp32 decode epilogue, the form every level outside the launch's ranges takes)
+_HEAD_PRED = os.environ.get("YOLOX_AMD_HEAD_PRED", "1") != "0"
+# feature widths head_pred2 is built for (head.hip): the six presets' head widths
+HEAD_PRED_WIDTHS = (64, 96, 128, 192, 256, 320)
 
 
 class PlanCtx:
     def __init__(self, batch: int, dtype: torch.dtype, device: torch.device, fuse_stem: bool = True,
-                 fuse_bottleneck: bool = _FUSE_BOTTLENECK, fuse_stem_s2: bool = True, csp_fusion: Optional[bool] = None):
+                 fuse_bottleneck: bool = _FUSE_BOTTLENECK, fuse_stem_s2: bool = True, csp_fusion: Optional[bool] = None,
+                 fuse_head_pred: bool = _HEAD_PRED):
         if dtype not in (torch.float32, torch.bfloat16, torch.float16):
             raise ValueError(f"compute dtype {dtype} not supported (float32, bfloat16, float16)")
         self.batch = batch
@@ -141,6 +147,8 @@ class PlanCtx:
         self.input_dtype = torch.uint8
         # Bottleneck conv1 (1x1) folded into conv2's 3x3 (conv_ws fused tiles): 16-bit only
         self.fuse_bottleneck = fuse_bottleneck and dtype != torch.float32
+        # a head level's preds + decode as one head_pred launch (False: two 1x1 pred convs)
+        self.fuse_head_pred = fuse_head_pred
         self.buffers: list[Buffer] = []
         self.weights: list[WeightSpec] = []
         self.ops: list[OpRec] = []
@@ -428,8 +436,9 @@ class PlanCtx:
         train = mode
         h, w = cls_feat.lh, cls_feat.lw
         C = head.num_classes
-        if (self.dtype != torch.float32 and cls_feat.ch == reg_feat.ch and cls_feat.ch in (64, 128, 256)
-                and 65 <= C <= 80 and (h * w) % 4 == 0 and a_off % 4 == 0 and out.anchors % 4 == 0
+        if (self.fuse_head_pred and self.dtype != torch.float32 and cls_feat.ch == reg_feat.ch
+                and cls_feat.ch in HEAD_PRED_WIDTHS and 1 <= C <= 80
+                and (h * w) % 4 == 0 and a_off % 4 == 0 and out.anchors % 4 == 0
                 and not cls_feat.up and not reg_feat.up):
             # the three preds + cat + sigmoid + decode of the level as one launch (head.hip)
             ro = self._weights([(head.reg_preds[k], None), (head.obj_preds[k], None)], reg_feat.ch)
@@ -606,12 +615,16 @@ class Plan:
                  input_layout: int = N.NCHW, input_dtype: torch.dtype = torch.float32, train: bool = False,
                  fuse_stem: bool = True, chunk: Optional[int] = None, fuse_bottleneck: bool = _FUSE_BOTTLENECK,
                  parallel_chunks: bool = False, fuse_stem_s2: bool = True, stage: str = "full",
-                 head_inputs: Optional[list] = None, csp_fusion: Optional[bool] = None, block=None):
+                 head_inputs: Optional[list] = None, csp_fusion: Optional[bool] = None, block=None,
+                 fuse_head_pred: bool = _HEAD_PRED):
         """``stage``: "full" (image -> decoded rows), "features" (image -> the three PAFPN
         maps: YoloPafpn.forward), "head" (three feature maps of ``head_inputs`` shapes
         [(C, H, W)] -> decoded rows: YoloxHead.forward) or "block" (one building block of the
         module tree -- ``block.plan_block`` -- over one NCHW map of ``head_inputs[0]``'s shape, or
-        over the image when ``block.takes_image``: the blocks' standalone forward)."""
+        over the image when ``block.takes_image``: the blocks' standalone forward).
+        ``fuse_head_pred`` (YOLOX_AMD_HEAD_PRED, default on): each head level's three preds + decode as
+        one head_pred launch where it is built (16-bit, 1-80 classes, head widths 64 / 96 / 128 / 192 /
+        256 / 320); off: the two 1x1 pred convs per level, for A/B runs and tests."""
         if stage not in ("full", "features", "head", "block"):
             raise ValueError(f"unknown plan stage {stage!r}")
         self.stage = stage
@@ -636,7 +649,7 @@ class Plan:
         head = model.head
         self.num_classes = head.num_classes if head is not None else 0
         ctx = PlanCtx(chunk, dtype, self.device, fuse_stem=fuse_stem, fuse_bottleneck=fuse_bottleneck,
-                      fuse_stem_s2=fuse_stem_s2, csp_fusion=csp_fusion)
+                      fuse_stem_s2=fuse_stem_s2, csp_fusion=csp_fusion, fuse_head_pred=fuse_head_pred)
         ctx.input_layout, ctx.input_dtype = input_layout, input_dtype
         if stage == "head":
             if chunk != batch or not head_inputs or len(head_inputs) != 3:
@@ -1157,17 +1170,18 @@ class Plan:
     def enable_scores(self) -> Optional[torch.Tensor]:
         """Have the head launches also write per-anchor serving records [B, A, 8] fp32
         {obj * max class, max class, class index, obj, cx, cy, w, h} (yxh_head_desc.scores), which
-        ``postprocess_device(..., scores=)`` filters instead of the rows (32 instead of 340 bytes read
-        per anchor).  The records belong to the forward that wrote the output
-        rows: the next forward overwrites them.  Eval decode plans whose every level is one
-        head_pred launch over 64 / 128 / 256 16-bit channels only; returns None (nothing enabled)
-        otherwise.  Call before capture()."""
+        ``postprocess_device(..., scores=)`` filters instead of the rows (32 bytes read per anchor
+        instead of the whole row).  The records belong to the forward that wrote the output
+        rows: the next forward overwrites them.  The row length the filter no longer reads is
+        4 * (5 + C) bytes (340 for COCO's 80 classes).  Eval decode plans whose every level is one
+        head_pred launch only (16-bit, 1-80 classes, head widths 64 / 96 / 128 / 192 / 256 / 320: every
+        preset); returns None (nothing enabled) otherwise.  Call before capture()."""
         if self._graph is not None or self._graph_alt is not None:
             raise RuntimeError("enable_scores() before capture()")
         heads = [r for r in self.ctx.ops if r.kind == N.OP_HEAD]
         other = [r for r in self.ctx.ops if r.kind == N.OP_CONV and (r.args["dst_f32"] or r.args.get("head_post"))]
         if (self.stage != "full" or not heads or other or self.ctx.dtype == torch.float32
-                or any(r.args["cin"] not in (64, 128, 256) or r.args["train"] != PlanCtx.HEAD_EVAL for r in heads)):
+                or any(r.args["cin"] not in HEAD_PRED_WIDTHS or r.args["train"] != PlanCtx.HEAD_EVAL for r in heads)):
             return None
         if self.scores is None:
             self.scores = torch.zeros(self.batch, self.anchors, 8, dtype=torch.float32, device=self.device)

@@ -226,12 +226,18 @@ class YoloxModule(nn.Module):
 
     @classmethod
     def synthetic(cls, name: str = "yolox_s", seed: int = 0, device: Optional[str] = None,
-                  dtype: torch.dtype = torch.float32) -> "YoloxModule":
+                  dtype: torch.dtype = torch.float32, num_classes: Optional[int] = None) -> "YoloxModule":
         """A fresh model of preset ``name`` with seeded weights and calibrated BN
-        statistics (yolox_amd.weights) -- used by tests and the benchmark."""
+        statistics (yolox_amd.weights) -- used by tests and the benchmark.  ``num_classes``:
+        the preset with that many classes (a fine-tuned model's head: only ``cls_preds`` change
+        shape, the BN statistics stay the preset's); None keeps the preset's 80."""
         from ..weights import synthetic_state_dict
 
         cfg = named_config(name)
+        if num_classes is not None:
+            if int(num_classes) < 1:
+                raise ValueError(f"num_classes must be positive, got {num_classes}")
+            cfg.num_classes = int(num_classes)
         model = cfg.get_model()
         model.load_state_dict(synthetic_state_dict(model.state_dict(), seed=seed, bn_stats=cfg.name))
         model = model.to(device or default_device(), dtype)
