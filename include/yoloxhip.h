@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define YXH_ABI_VERSION 18
+#define YXH_ABI_VERSION 19
 
 enum yxh_status {
     YXH_OK = 0,
@@ -103,14 +103,27 @@ typedef struct {
     int64_t dst_bstride;
     float decode_stride; /* level stride for DECODE acts                                */
     int32_t decode_coff; /* position of output channel 0 in the 5+C row (0 or 5)       */
-    int32_t tile;        /* 0: heuristic; else 2*id + (slabs-1): id 1-9 explicit tile
-                            (TN x TM) of the register-staged kernel, id 17-25 the same
-                            tiles on the LDS-DMA kernel, id 33-51 the row-tiled 3x3
-                            kernel, id 65-70 the persistent streaming 1x1 kernel;
-                            for the weight-stationary 1x1 ids 201-210 / 241-258 the low
-                            bit instead selects the 16-byte-store epilogue (round 6; a
-                            tile without it refuses the odd code); chosen by the
-                            planner's on-device autotune                                 */
+    int32_t tile;        /* 0: by-shape default; else 2*id + low bit, chosen by the planner's
+                            on-device autotune.  The ids (yxh_conv_tile_family reports this
+                            table; an id in no row is YXH_EINVAL):
+                              ids      name      kernel                              low bit
+                              1-9      igemm     register-staged conv_igemm          K slabs - 1
+                              17-25    glds      the same tiles, LDS-DMA conv_glds   K slabs - 1
+                              33-51    rows      row-tiled 3x3 conv_rows             K slabs - 1
+                              65-70    pw        persistent streaming 1x1 conv_pw    K slabs - 1
+                              81-82    pwr       register-operand 1x1 conv_pwr       -
+                              97-104   pwf       dense 1x1 conv_pwf                  -
+                              113-160  r3        3x3 conv_r3 (buffer-LDS loader)     -
+                              161-190  ws        weight-stationary 3x3 conv_ws       -
+                              191-196  ws_fused  conv_ws + fused Bottleneck conv1    -
+                              201-210  ws1       weight-stationary 1x1 conv_ws1      16-byte stores
+                              211-214  pw1f      fp32 1x1 GEMM conv_pw1f             -
+                              215-220  dgrad_s2  3x3 s2 data gradient by parity      -
+                              221-236  ws_post   conv_ws + 1x1 post conv             -
+                              241-258  ws1_deep  conv_ws1, deep row pipelines        16-byte stores
+                              261-289  ws_wide   conv_ws, 80/160/320/512 channels    -
+                            ("16-byte stores": the odd code asks for that epilogue; a tile
+                            without it refuses the odd code.)                             */
     int32_t flags;       /* YXH_CONV_ACCUMULATE: f32 dst += result (gradient accumulation) */
     int32_t grid_cap;    /* 0, or the CUs the persistent tiles (conv_ws / conv_ws1 / conv_pwf) may occupy: a
                             graph lane running beside another lane's work leaves it the rest of the chip */
@@ -165,6 +178,24 @@ typedef struct {
 #define YXH_CONV_POST_STORE 4
 
 int yxh_conv2d(const yxh_conv_desc* d, void* stream);
+
+/*
+ * yxh_conv_tile_family (ABI 19): row `index` (0, 1, ...) of the yxh_conv_desc.tile id table, in
+ * increasing order of `first`; YXH_EINVAL past the last row.  Needs no device.
+ */
+#define YXH_TILE_BIT_SLABS 1   /* the code's low bit is K slabs - 1                                   */
+#define YXH_TILE_BIT_V16 2     /* the code's low bit asks for the 16-byte-store epilogue             */
+#define YXH_TILE_POST 4        /* runs a conv with a post conv (post_weight); no other row does      */
+#define YXH_TILE_GROUPS2 8     /* runs YXH_CONV_GROUPS2 (without a post conv); no other row does     */
+#define YXH_TILE_PRE 16        /* accepts pre_weight at this level: only ws_fused runs the fused
+                                  Bottleneck, the other rows' kernels refuse it themselves           */
+#define YXH_TILE_NO_DILATED 32 /* refuses sources with upsample == 2                                 */
+typedef struct {
+    char name[16];
+    int32_t first, count; /* public ids first .. first + count - 1                                  */
+    int32_t flags;        /* YXH_TILE_*                                                             */
+} yxh_tile_family;
+int yxh_conv_tile_family(int32_t index, yxh_tile_family* out);
 
 /*
  * yxh_focus_pack: Focus space-to-depth (network_blocks.py:193-208, channel order

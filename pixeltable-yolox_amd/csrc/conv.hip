@@ -18,10 +18,6 @@
 
 namespace yxh {
 
-// conv_ws tiles for 80 / 160 / 320 / 512 input channels (yolox_x, yolox_l) and the fp32-gradient
-// forms (tiles 281-288): tile ids 261..260+kNumWsWideTiles (conv_ws_dispatch ids 61..)
-constexpr int kNumWsWideTiles = 29;
-
 // ---------------------------------------------------------------- implicit GEMM
 // Block: 256 threads = 4 waves on a WR x WC grid; tile TN output channels x TM
 // output pixels; KS 64-byte K slabs per pipeline stage.  LDS holds two stages; a
@@ -416,14 +412,9 @@ int launch_igemm(const ConvParams& p, int ks, hipStream_t st) {
     return YXH_OK;
 }
 
-// Tile configurations (id -> TN x TM, wave grid).  yxh_conv_desc.tile = id * 2 + (KS - 1)
-// selects one explicitly (the planner autotunes it per layer on the device); 0 picks
-// by a block-count heuristic.
-struct TileCfg { int tn, tm; };
-constexpr TileCfg kTiles[] = {{0, 0},     {16, 256}, {32, 256}, {32, 128}, {64, 256},
-                              {64, 128},  {64, 64},  {80, 128}, {128, 128}, {128, 64}};
-constexpr int kNumTiles = sizeof(kTiles) / sizeof(kTiles[0]);
-
+// conv_igemm's tile configurations (id -> TN x TM, wave grid): the "igemm" family of conv_tiles.hpp,
+// whose public ids are these.  yxh_conv_desc.tile = id * 2 + (KS - 1) selects one explicitly (the
+// planner autotunes it per layer on the device); 0 picks by a block-count heuristic.
 template <typename T>
 int launch_tile(int id, const ConvParams& p, int ks, hipStream_t st) {
     switch (id) {
@@ -448,6 +439,17 @@ int heuristic_tile(const ConvParams& p) {
     if (p.cout <= 64) return blocks(64, 256) >= target ? 4 : blocks(64, 128) >= target ? 5 : 6;
     if (p.cout <= 80) return 7;
     return blocks(128, 128) >= target ? 8 : blocks(128, 64) >= target ? 9 : 6;
+}
+
+// Route public id `id` (in a row: checked by the caller, or one of conv_tiles.hpp's defaults)
+int run_tile(int dt, int id, const ConvParams& p, int ks, hipStream_t st) {
+    const TileFamily* f = find_family(id);
+    return f->fn(dt, id - f->first + f->local_first, p, ks, st);
+}
+
+int refuse(const char* what, const TileFamily& f) {
+    set_error("%s tiles (ids %d-%d) only", what, f.first, f.last());
+    return YXH_EUNSUPPORTED;
 }
 
 }  // namespace
@@ -554,6 +556,8 @@ int conv2d(const yxh_conv_desc* d, hipStream_t st) {
     const int cus = device_cus();
     p.cus = d->grid_cap > 0 && d->grid_cap < cus ? d->grid_cap : cus;
     p.grp2 = grp2 ? 1 : 0;
+    // the row of an explicit tile code (conv_tiles.hpp); null for the defaults and for an id in no row
+    const TileFamily* asked = d->tile > 0 ? find_family(d->tile >> 1) : nullptr;
     if (d->post_weight) {
         // a 1x1 post conv (or the head form: two groups, each with its own preds) runs on the
         // conv_ws post tiles; dispatched here, after the grid / weight-copy fields are set
@@ -597,29 +601,28 @@ int conv2d(const yxh_conv_desc* d, hipStream_t st) {
                       "YXH_CONV_POST_STORE: a 1x1 post conv (not the head form) and a 16-bit dst of 8-byte rows");
         if (d->tile == 0) {  // default post tile per shape
             const bool chain = d->post_src.channels == 0 && d->stride == 1;
-            return conv_ws_dispatch(
-                dt, head ? 51 : d->stride == 2 ? 45 : chain ? (d->cin == 64 ? 54 : 55) : d->cin == 32 ? 41 : 43, p, st);
+            const int id = head             ? kTileHeadForm
+                           : d->stride == 2 ? kTilePostStride2
+                           : chain          ? (d->cin == 64 ? kTilePostChain64 : kTilePostChain128)
+                                            : (d->cin == 32 ? kTilePost32 : kTilePost64);
+            return run_tile(dt, id, p, 0, st);
         }
-        if (!((d->tile >> 1) > 220 && (d->tile >> 1) <= 220 + kNumWsPostTiles)) {
-            set_error("a post conv runs on the conv_ws post tiles (ids 221-%d) only", 220 + kNumWsPostTiles);
-            return YXH_EUNSUPPORTED;
-        }
-        return conv_ws_dispatch(dt, (d->tile >> 1) - 220 + 40, p, st);
+        if (!asked || !(asked->flags & YXH_TILE_POST))
+            return refuse("a post conv runs on the conv_ws post", family_with(YXH_TILE_POST));
+        return run_tile(dt, d->tile >> 1, p, 0, st);
     }
-    if (grp2 && d->tile == 0) return conv_ws_dispatch(dt, d->cin == 256 ? 176 - 160 : 185 - 160, p, st);
-    if (grp2 && !((d->tile >> 1) > 160 && (d->tile >> 1) <= 190)) {
-        set_error("YXH_CONV_GROUPS2 runs on the plain conv_ws tiles (ids 161-190) only");
-        return YXH_EUNSUPPORTED;
-    }
+    if (grp2 && d->tile == 0) return run_tile(dt, d->cin == 256 ? kTileGroups2_256 : kTileGroups2_128, p, 0, st);
+    if (grp2 && (!asked || !(asked->flags & YXH_TILE_GROUPS2)))
+        return refuse("YXH_CONV_GROUPS2 runs on the plain conv_ws", family_with(YXH_TILE_GROUPS2));
     YXH_CHECK_ARG(!d->pre_weight || (d->pre_bias && aligned16(d->pre_weight) && d->kh == 3 && d->stride == 1 &&
                                      d->pad == 1 && d->groups == 1 && d->nsrc == 1 && dt != YXH_F32),
                   "fused Bottleneck: 16-bit 3x3 s1 conv over one source with a pre_bias");
     if (d->pre_weight && d->tile == 0)  // default fused tile per channel count
-        return conv_ws_dispatch(dt, d->cin == 32 ? 191 - 160 : d->cin == 64 ? 194 - 160 : 195 - 160, p, st);
-    if (d->pre_weight && (d->tile >> 1) <= 160 + 30) {
-        set_error("fused Bottleneck runs on the conv_ws fused tiles (ids 191-196) only");
-        return YXH_EUNSUPPORTED;
-    }
+        return run_tile(dt, d->cin == 32 ? kTileFused32 : d->cin == 64 ? kTileFused64 : kTileFused128, p, 0, st);
+    // (an id in no row: refused here below the fused tiles, as a bad tile code further down above them)
+    const TileFamily& fused = family_with(YXH_TILE_PRE);
+    if (d->pre_weight && (asked ? !(asked->flags & YXH_TILE_PRE) : (d->tile >> 1) < fused.first))
+        return refuse("fused Bottleneck runs on the conv_ws fused", fused);
     p.vec16 = d->dst_dtype == dt && ((uintptr_t)d->dst % 16) == 0 && (d->dst_cstride * des) % 16 == 0 &&
               (d->dst_bstride * des) % 16 == 0 && (d->cout * des) % 16 == 0;
 
@@ -640,50 +643,36 @@ int conv2d(const yxh_conv_desc* d, hipStream_t st) {
     // fall on a chunk boundary -- checked above -- not on a stage boundary: yolox_x's
     // 80/160/320-channel CSP halves)
     int ks = d->cin >= k2 ? 2 : 1;
-    int tile = heuristic_tile(p);
+    int tile = heuristic_tile(p);  // an igemm id
     if (d->tile > 0) {
         tile = d->tile >> 1;
         const int want_ks = (d->tile & 1) + 1;
-        YXH_CHECK_ARG((tile > 0 && tile < kNumTiles) || (tile > 16 && tile < 16 + kNumTiles) ||
-                          (tile > 32 && tile <= 32 + kNumRowTiles) || (tile > 64 && tile <= 64 + kNumPwTiles) ||
-                          (tile > 80 && tile <= 80 + kNumPwrTiles) || (tile > 96 && tile <= 96 + kNumPwfTiles) ||
-                          (tile > 112 && tile <= 112 + kNumR3Tiles) || (tile > 160 && tile <= 160 + kNumWsTiles) ||
-                          (tile > 200 && tile <= 200 + kNumWs1Tiles) || (tile > 210 && tile <= 210 + kNumPw1fTiles) ||
-                          (tile > 214 && tile <= 214 + kNumDgradS2Tiles) ||
-                          (tile > 220 && tile <= 220 + kNumWsPostTiles) ||
-                          (tile > 240 && tile <= 240 + kNumWs1DeepTiles) ||
-                          (tile > 260 && tile <= 260 + kNumWsWideTiles),
-                      "tile %d", d->tile);
+        YXH_CHECK_ARG(asked, "tile %d", d->tile);
         YXH_CHECK_ARG(want_ks == 1 || ks == 2, "2-slab staging not possible for this conv");
         ks = want_ks;
     }
     const int kstage = 4 * ks * epc;
     p.ncb = (d->cin + kstage - 1) / kstage;
-    if (tile > 260) return conv_ws_dispatch(dt, tile - 260 + 60, p, st);
-    // conv_ws1 (tiles 201-210, 241-258): the slab bit selects the 16-byte-store epilogue (conv_ws1.hip V16, where
-    // the destination rows allow it; tiles without it refuse the odd code); the autotuner times both codes.  (The
-    // same epilogue in conv_ws measured neutral on the bench and was dropped)
-    if ((tile > 240 && tile <= 240 + kNumWs1DeepTiles) || (tile > 200 && tile <= 200 + kNumWs1Tiles))
-        p.v16_req = ks == 2;
-    if (tile > 240) return conv_ws1_dispatch(dt, tile - 240 + kNumWs1Tiles, p, st);
-    if (tile > 220) return conv_ws_dispatch(dt, tile - 220 + 40, p, st);
-    if (tile > 214) return dgrad_s2f_dispatch(dt, tile - 214, p, st);
-    if (dilated && tile > 16) {
-        set_error("dilated (upsample == 2) sources run on the register-staged kernel only (tile ids 1-9)");
+    const TileFamily& fam = *find_family(tile);
+    // conv_ws1: the low bit selects the 16-byte-store epilogue (conv_ws1.hip V16, where the destination rows
+    // allow it; tiles without it refuse the odd code); the autotuner times both codes.  (The same epilogue in
+    // conv_ws measured neutral on the bench and was dropped)
+    if (fam.flags & YXH_TILE_BIT_V16) p.v16_req = ks == 2;
+    if (dilated && (fam.flags & YXH_TILE_NO_DILATED)) {
+        const TileFamily& reg = kTileFamilies[0];
+        set_error("dilated (upsample == 2) sources run on the register-staged kernel only (tile ids %d-%d)", reg.first,
+                  reg.last());
         return YXH_EUNSUPPORTED;
     }
-    if (tile > 210) return conv_pw1f_dispatch(dt, tile - 210, p, st);
-    if (tile > 200) return conv_ws1_dispatch(dt, tile - 200, p, st);
-    if (tile > 160) return conv_ws_dispatch(dt, tile - 160, p, st);
-    if (tile > 112) return conv_r3_dispatch(dt, tile - 112, p, st);
-    if (tile > 96) return conv_pwf_dispatch(dt, tile - 96, p, st);
-    if (tile > 80) return conv_pwr_dispatch(dt, tile - 80, p, st);
-    if (tile > 64) return conv_pw_dispatch(dt, tile - 64, p, ks, st);
-    if (tile > 32) return conv_rows_dispatch(dt, tile - 32, p, ks, st);
-    if (tile > 16) return conv_glds_dispatch(dt, tile - 16, p, ks, st);
-    if (dt == YXH_BF16) return launch_tile<bf16>(tile, p, ks, st);
-    if (dt == YXH_F16) return launch_tile<f16>(tile, p, ks, st);
-    return launch_tile<float>(tile, p, ks, st);
+    return run_tile(dt, tile, p, ks, st);
+}
+
+// The igemm row's dispatch.  (Defined below conv2d: the kernels are emitted in the order the host code
+// first names them, and the code object keeps the layout it had.)
+int conv_igemm_dispatch(int dtype, int id, const ConvParams& p, int ks, hipStream_t st) {
+    if (dtype == YXH_BF16) return launch_tile<bf16>(id, p, ks, st);
+    if (dtype == YXH_F16) return launch_tile<f16>(id, p, ks, st);
+    return launch_tile<float>(id, p, ks, st);
 }
 
 int focus_pack_launch(const void* img, int layout, int idt, int B, int H, int W, void* dst, int odt,

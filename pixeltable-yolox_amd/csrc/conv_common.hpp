@@ -1,6 +1,7 @@
 // Pieces shared by the conv kernels (conv.hip, conv_glds.hip).
 #pragma once
 
+#include "conv_tiles.hpp"  // every family's dispatch function and the tile-id table that routes to them
 #include "yxh_common.hpp"
 
 namespace yxh {
@@ -283,40 +284,5 @@ __device__ __forceinline__ void conv_epilogue(const ConvParams& p, f32x4 (&acc)[
     conv_epilogue_map<T, TN, TM, WR, WC, SMEM_BYTES>(
         p, acc, smem, [m0, M](int pl) { return m0 + pl < M ? m0 + pl : -1; }, n0, bias);
 }
-
-// LDS-DMA variant (conv_glds.hip); id as in conv.hip's tile table
-int conv_glds_dispatch(int dtype, int id, const ConvParams& p, int ks, hipStream_t st);
-// Row-tiled 3x3 conv (conv_rows.hip): 2D output tiles, kx taps share one LDS row image
-int conv_rows_dispatch(int dtype, int id, const ConvParams& p, int ks, hipStream_t st);
-constexpr int kNumRowTiles = 19;
-// Persistent streaming 1x1 conv (conv_pw.hip): tile ids 65..64+kNumPwTiles
-int conv_pw_dispatch(int dtype, int id, const ConvParams& p, int ks, hipStream_t st);
-constexpr int kNumPwTiles = 6;
-// Register-operand 1x1 conv (conv_pwr.hip): tile ids 81..80+kNumPwrTiles
-int conv_pwr_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st);
-constexpr int kNumPwrTiles = 2;
-// VALU-free-loop dense 1x1 conv (conv_pwf.hip): tile ids 97..96+kNumPwfTiles
-int conv_pwf_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st);
-constexpr int kNumPwfTiles = 8;
-// 3x3 conv with the branch-free buffer-LDS loader (conv_r3.hip): tile ids 113..112+kNumR3Tiles
-int conv_r3_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st);
-constexpr int kNumR3Tiles = 48;  // ids beyond the built ones report EINVAL
-// Weight-stationary persistent 3x3 conv (conv_ws.hip): tile ids 161..160+kNumWsTiles
-int conv_ws_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st);
-constexpr int kNumWsTiles = 36;  // 31..36: fused Bottleneck (pre_weight)
-// conv_ws tiles with a 1x1 post conv (yxh_conv_desc.post_weight): tile ids 221..220+kNumWsPostTiles
-// (conv_ws_dispatch ids 41..40+kNumWsPostTiles)
-constexpr int kNumWsPostTiles = 16;
-// Weight-stationary persistent 1x1 conv over dense sources (conv_ws1.hip): tile ids 201..200+kNumWs1Tiles
-int conv_ws1_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st);
-constexpr int kNumWs1Tiles = 10;
-// ... and its deep row pipelines (conv_ws1 ids 11..10+kNumWs1DeepTiles): tile ids 241..240+kNumWs1DeepTiles
-constexpr int kNumWs1DeepTiles = 18;  // 249-252, 256: upsampled source 0; 253-258: full-width (round 5)
-// fp32 1x1 GEMM for the training path, k-minor MFMA operands (conv_pw1f.hip): tile ids 211..210+kNumPw1fTiles
-int conv_pw1f_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st);
-constexpr int kNumPw1fTiles = 4;
-// fp32 data gradient of a 3x3 s2 conv by output parity class (conv_pw1f.hip): tile ids 215..216
-int dgrad_s2f_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st);
-constexpr int kNumDgradS2Tiles = 6;  // 215-216 fp32 (dgrad_s2f), 217-220 16-bit (dgrad_s2h)
 
 }  // namespace yxh

@@ -218,8 +218,8 @@ static int launch_rows(const ConvParams& p, hipStream_t st) {
     }
 }
 
-// Variant table (yoloxhip.h tile ids 33..32+kNumRowTiles): output tile TX x TY, TN, NBUF.
-// Ids 1-6 exist for every dtype, 7+ for bf16/f16 only.
+// Variant table (the "rows" family of conv_tiles.hpp): output tile TX x TY, TN, NBUF.
+// Ids 1-6 exist for every dtype, 7-19 for bf16/f16 only.
 template <typename T, int S, int CH>
 static int dispatch_shape(int id, const ConvParams& p, hipStream_t st) {
     switch (id) {
@@ -248,7 +248,7 @@ static int dispatch_shape(int id, const ConvParams& p, hipStream_t st) {
             case 19: return launch_rows<T, S, 64, 2, CH, 64, 2>(p, st);
             default: break;
         }
-    } else if (id > 6 && id <= kNumRowTiles) {
+    } else if (id > 6 && id <= 19) {
         set_error("conv_rows variant %d is built for bf16/f16 only", id);
         return YXH_EUNSUPPORTED;
     }

@@ -8,6 +8,7 @@
 #include <atomic>
 #include <vector>
 
+#include "conv_tiles.hpp"
 #include "yxh_common.hpp"
 
 namespace yxh {
@@ -133,6 +134,17 @@ size_t yxh_sizeof_op(void) { return sizeof(yxh_op); }
 size_t yxh_sizeof_conv_desc(void) { return sizeof(yxh_conv_desc); }
 
 int yxh_conv2d(const yxh_conv_desc* d, void* stream) { return conv2d(d, (hipStream_t)stream); }
+
+int yxh_conv_tile_family(int32_t index, yxh_tile_family* out) {
+    YXH_CHECK_ARG(out, "null tile family");
+    YXH_CHECK_ARG(index >= 0 && index < kNumTileFamilies, "tile family index %d", index);
+    const TileFamily& f = kTileFamilies[index];
+    snprintf(out->name, sizeof(out->name), "%s", f.name);
+    out->first = f.first;
+    out->count = f.count;
+    out->flags = f.flags;
+    return YXH_OK;
+}
 
 int yxh_head_pred(const yxh_head_desc* d, void* stream) { return head_pred_launch(d, (hipStream_t)stream); }
 

@@ -17,7 +17,7 @@ import torch  # noqa: F401  (must precede loading the HIP library)
 LIB_PATH = os.environ.get(
     "YOLOX_AMD_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "libyoloxhip.so"))
 
-ABI_VERSION = 18
+ABI_VERSION = 19
 
 # enums (yoloxhip.h)
 OK, EINVAL, EHIP, EUNSUPPORTED = 0, -1, -2, -3
@@ -57,6 +57,11 @@ class ConvDesc(C.Structure):
 CONV_ACCUMULATE = 1
 CONV_GROUPS2 = 2
 CONV_POST_STORE = 4
+
+
+class TileFamily(C.Structure):
+    """yxh_tile_family: one row of the yxh_conv_desc.tile id table (mirrored by tiles.py)."""
+    _fields_ = [("name", C.c_char * 16), ("first", C.c_int32), ("count", C.c_int32), ("flags", C.c_int32)]
 
 
 class OptSeg(C.Structure):
@@ -189,6 +194,7 @@ def lib():
             "yxh_sizeof_op": ([], sz),
             "yxh_sizeof_conv_desc": ([], sz),
             "yxh_conv2d": ([C.POINTER(ConvDesc), vp], C.c_int),
+            "yxh_conv_tile_family": ([i32, C.POINTER(TileFamily)], C.c_int),
             "yxh_head_pred": ([C.POINTER(HeadDesc), vp], C.c_int),
             "yxh_focus_pack": ([vp, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
             "yxh_spp_maxpool": ([vp, i32, i32, i32, i32, i32, i32, i64, vp], C.c_int),
@@ -258,8 +264,8 @@ def lib():
     return _lib
 
 
-EXPORTED = ["yxh_abi_version", "yxh_last_error", "yxh_sizeof_op", "yxh_sizeof_conv_desc", "yxh_conv2d", "yxh_head_pred",
-            "yxh_focus_pack", "yxh_spp_maxpool", "yxh_stem_conv", "yxh_stem_s2", "yxh_stem_pack", "yxh_fold_bn_pack", "yxh_letterbox_batch", "yxh_augment_batch", "yxh_sizeof_aug_image", "yxh_postprocess_workspace_bytes", "yxh_set_nms_mask_budget",
+EXPORTED = ["yxh_abi_version", "yxh_last_error", "yxh_sizeof_op", "yxh_sizeof_conv_desc", "yxh_conv2d", "yxh_conv_tile_family",
+            "yxh_head_pred", "yxh_focus_pack", "yxh_spp_maxpool", "yxh_stem_conv", "yxh_stem_s2", "yxh_stem_pack", "yxh_fold_bn_pack", "yxh_letterbox_batch", "yxh_augment_batch", "yxh_sizeof_aug_image", "yxh_postprocess_workspace_bytes", "yxh_set_nms_mask_budget",
             "yxh_postprocess", "yxh_postprocess_ev", "yxh_postprocess_split", "yxh_postprocess_scored", "yxh_yolox_loss_workspace_bytes", "yxh_yolox_loss", "yxh_run_ops", "yxh_graph_create", "yxh_graph_create_lanes", "yxh_graph_create_dag",
             "yxh_graph_launch", "yxh_graph_destroy", "yxh_reduce_workspace_bytes", "yxh_bn_stats", "yxh_bn_act_fwd",
             "yxh_bn_act_bwd", "yxh_channel_sum", "yxh_conv_wgrad", "yxh_pack_dgrad_weight", "yxh_pack_weights_batch", "yxh_pack_frag", "yxh_spp_bwd",

@@ -26,6 +26,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
+from . import tiles as T
 
 ALIGN = 256
 
@@ -465,19 +466,29 @@ class OutBuffer:
     row: int  # 5 + C
 
 
-# tile codes (2 * id + slabs - 1); ids 1-9 register-staged conv_igemm, 17-25 the same
-# tiles on the LDS-DMA conv_glds kernel, 33-51 the row-tiled 3x3 conv_rows kernel,
-# 65-70 the persistent streaming 1x1 conv_pw kernel, 81-82 the register-operand 1x1
-# conv_pwr kernel, 97-104 the dense 1x1 conv_pwf kernel, 113-150 the 3x3 conv_r3 kernel
-# (yoloxhip.h yxh_conv_desc.tile); for the weight-stationary 1x1 conv_ws1 (201-210, 241-258) the slab bit
-# selects the 16-byte-store epilogue instead (round 6)
-TILE_CANDIDATES = [2 * i + k for i in list(range(1, 10)) + list(range(17, 26)) + list(range(33, 52))
-                   + list(range(65, 71)) for k in (0, 1)] + [2 * 81, 2 * 82] + [2 * i for i in range(97, 105)] + [2 * i for i in range(113, 153)] + [2 * i for i in range(161, 197)] + [2 * i + k for i in range(201, 211) for k in (0, 1)] + [2 * i for i in range(221, 237)] + [2 * i + k for i in range(241, 259) for k in (0, 1)] + [2 * i for i in range(261, 281)]
+# Tile codes the autotuner times, family by family (tiles.py holds the id table and what the low bit
+# means per family: both bits where it selects K slabs or conv_ws1's 16-byte-store epilogue).  The order
+# decides ties.  Left out: dgrad_s2 / pw1f (training only) and ws_wide's fp32-gradient and stem forms.
+TILE_CANDIDATES = [
+    *T.codes(T.IGEMM.ids, (0, 1)),
+    *T.codes(T.GLDS.ids, (0, 1)),
+    *T.codes(T.ROWS.ids, (0, 1)),
+    *T.codes(T.PW.ids, (0, 1)),
+    *T.codes(T.PWR.ids),
+    *T.codes(T.PWF.ids),
+    *T.codes(T.R3_BUILT),
+    *T.codes(T.WS.ids),
+    *T.codes(T.WS_FUSED.ids),
+    *T.codes(T.WS1.ids, (0, 1)),
+    *T.codes(T.WS_POST.ids),
+    *T.codes(T.WS1_DEEP.ids, (0, 1)),
+    *T.codes(T.WS_WIDE_16),
+]
 # 16-bit plans: the families that win on MI355X (profiles/r03/final/tune_r3fa_*.json: yolox_s picks only
 # conv_pwf / conv_ws / conv_ws1; yolox_l fp16 also conv_igemm and conv_r3 once or twice); the LDS-DMA
 # conv_glds, row-tiled conv_rows and the round-1 pointwise kernels never do and are tried only with
 # YOLOX_AMD_TUNE_ALL_FAMILIES=1 (fp32 plans always try every family)
-TILE_CANDIDATES_16 = [t for t in TILE_CANDIDATES if (t >> 1) < 17 or (t >> 1) > 96]
+TILE_CANDIDATES_16 = [t for t in TILE_CANDIDATES if T.family_of(t) not in (T.GLDS, T.ROWS, T.PW, T.PWR)]
 _TUNE_ALL_FAMILIES = os.environ.get("YOLOX_AMD_TUNE_ALL_FAMILIES", "0") == "1"
 # CUs a graph lane's persistent conv grids may occupy ("lane:cus,..."; yxh_conv_desc.grid_cap): a head
 # level forked early (YOLOX_AMD_GRAPH=streams) leaves the rest of the chip to the neck it runs beside

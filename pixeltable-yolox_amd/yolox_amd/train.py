@@ -35,6 +35,7 @@ import torch
 import torch.nn as nn
 
 from . import _native as N
+from . import tiles as T
 from .models.losses import LOSS_KEYS
 from .models.network import (BaseConv, Bottleneck, CspDarknet, CspLayer, DWConv, Focus, SPPBottleneck,
                              YoloPafpn, YoloxHead)
@@ -130,21 +131,32 @@ class GradBuffer:
 
 # Tiles of the training convolutions, picked on the device the first time a shape runs
 # (HIP events around each candidate, outputs redirected to scratch) and cached for the
-# process.  Forward/data-gradient convs: the conv_igemm, conv_glds and conv_rows
-# families, plus the conv_r3h tiles on fp32 (tile codes as engine.TILE_CANDIDATES); weight
-# gradients: yxh_wgrad_desc
-# tiles 1-10.  YOLOX_AMD_TRAIN_TUNE=0 keeps the by-shape defaults.
-_BASE_TILES = [2 * i + k for i in list(range(1, 10)) + list(range(17, 26)) + list(range(33, 52)) for k in (0, 1)]
-# 16-bit (autocast) steps also try the inference path's 16-bit kernels for the forward convs: dense
-# 1x1 conv_pwf (97-104), weight-stationary 3x3 conv_ws (161-190, 261-280: yolox_x / yolox_l widths) and
-# 1x1 conv_ws1 (201-210); of those conv_ws's fp32-gradient tiles (281-288, stride-1 3x3s) and conv_pwf
-# (1x1s, round 5) take the data gradient's fp32-accumulating form; stride-2 3x3 data gradients also try the
-# parity-class tiles (217-220, dgrad_s2h: 1/2/2/4 taps instead of 9 over a zero-dilated dy)
-CONV_TUNE_TILES = _BASE_TILES + ([] if os.environ.get("YOLOX_AMD_TRAIN_TILES16") == "base" else
-                                 [2 * i for i in list(range(97, 105)) + list(range(161, 191)) + list(range(201, 211))
-                                  + list(range(261, 290)) + list(range(217, 221))])
-CONV_TUNE_TILES_F32 = _BASE_TILES + [2 * (112 + i) for i in (29, 30, 31, 32, 33, 38, 39, 40)] + [2 * i for i in range(211, 217)]
-WGRAD_TUNE_TILES = list(range(1, 11)) + list(range(11, 17)) + list(range(17, 25)) + list(range(25, 31))
+# process.  Forward/data-gradient convs: tile codes of yxh_conv_desc.tile, built family by family from
+# tiles.py (the id table); the order decides ties.  Weight gradients: every tile of yxh_wgrad_desc (an id
+# space of its own).  YOLOX_AMD_TRAIN_TUNE=0 keeps the by-shape defaults.
+_BASE_TILES = T.codes(T.IGEMM.ids, (0, 1)) + T.codes(T.GLDS.ids, (0, 1)) + T.codes(T.ROWS.ids, (0, 1))
+
+
+def conv_tune_tiles() -> list:
+    """16-bit (autocast) steps: unless YOLOX_AMD_TRAIN_TILES16=base, the forward convs also try the inference
+    path's 16-bit kernels; of those ws_wide's fp32-gradient tiles (stride-1 3x3s) and conv_pwf (1x1s) take the
+    data gradient's fp32-accumulating form."""
+    if os.environ.get("YOLOX_AMD_TRAIN_TILES16") == "base":
+        return list(_BASE_TILES)
+    return [
+        *_BASE_TILES,
+        *T.codes(T.PWF.ids),      # dense 1x1
+        *T.codes(T.WS.ids),       # weight-stationary 3x3
+        *T.codes(T.WS1.ids),      # weight-stationary 1x1
+        *T.codes(T.WS_WIDE.ids),  # ... 3x3 at yolox_x / yolox_l widths, fp32-gradient forms, the stem conv
+        *T.codes(T.DGRAD_S2_16),  # stride-2 3x3 data gradients: 1/2/2/4 taps by parity class instead of 9
+    ]
+
+
+CONV_TUNE_TILES = conv_tune_tiles()
+# fp32 steps: the conv_r3h tiles built for fp32, the fp32 1x1 GEMM and the fp32 parity-class data gradient
+CONV_TUNE_TILES_F32 = _BASE_TILES + T.codes(T.R3H_F32) + T.codes(T.PW1F.ids) + T.codes(T.DGRAD_S2_F32)
+WGRAD_TUNE_TILES = list(range(1, 31))
 _TRAIN_TILES: dict = {}
 # YOLOX_AMD_TUNE_CHECK_DET=1 (tests): every applicable candidate also runs twice into a zeroed sink and
 # must write the same bytes both times; (shape key, tile) pairs that do not are collected here
