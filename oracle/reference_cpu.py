@@ -273,16 +273,11 @@ def iou_loss(pred: Tensor, target: Tensor) -> Tensor:
 
 
 # ----------------------------------------------------------------- SimOTA
-def simota_assign(gt_boxes: Tensor, gt_classes: Tensor, pred_boxes: Tensor, cls_logits: Tensor,
-                  obj_logits: Tensor, x_shifts: Tensor, y_shifts: Tensor, strides: Tensor,
-                  num_classes: int = 80):
-    """get_assignments + get_geometry_constraint + simota_matching for ONE image
-    (yolo_head.py:420-574).
-
-    gt_boxes [G,4] cxcywh, gt_classes [G], pred_boxes [A,4], cls_logits [A,C],
-    obj_logits [A,1], shifts/strides [A].  Returns (fg_mask [A] bool,
-    matched_gt_inds [F], pred_ious [F], gt_matched_classes [F], num_fg).
-    """
+def _simota_costs(gt_boxes: Tensor, gt_classes: Tensor, pred_boxes: Tensor, cls_logits: Tensor,
+                  obj_logits: Tensor, x_shifts: Tensor, y_shifts: Tensor, strides: Tensor, num_classes: int):
+    """get_geometry_constraint + the pairwise IoU / cost matrices of get_assignments
+    (yolo_head.py:445-487, :511-540).  Returns (anchor_filter [A] bool, ious [G, n], cost [G, n],
+    base [G, n] = the cost without its 1e6 geometry term)."""
     G = gt_boxes.shape[0]
     # geometry constraint, :511-540 (centre radius 1.5 strides, strict > 0)
     xc = ((x_shifts + 0.5) * strides)[None]
@@ -308,12 +303,33 @@ def simota_assign(gt_boxes: Tensor, gt_classes: Tensor, pred_boxes: Tensor, cls_
     cls_cost = F.binary_cross_entropy(p.unsqueeze(0).repeat(G, 1, 1),
                                       onehot.unsqueeze(1).repeat(1, n_in, 1), reduction="none").sum(-1)
     cost = cls_cost + 3.0 * iou_cost + float(1e6) * (~geom)
+    return anchor_filter, ious, cost, cls_cost + 3.0 * iou_cost
+
+
+def _dynamic_k(ious: Tensor):
+    """(top-min(10, n) IoU sums [G], dynamic_k [G]), yolo_head.py:545-547."""
+    topk, _ = torch.topk(ious, min(10, ious.size(1)), dim=1)
+    sums = topk.sum(1)
+    return sums, torch.clamp(sums.int(), min=1)
+
+
+def simota_assign(gt_boxes: Tensor, gt_classes: Tensor, pred_boxes: Tensor, cls_logits: Tensor,
+                  obj_logits: Tensor, x_shifts: Tensor, y_shifts: Tensor, strides: Tensor,
+                  num_classes: int = 80):
+    """get_assignments + get_geometry_constraint + simota_matching for ONE image
+    (yolo_head.py:420-574).
+
+    gt_boxes [G,4] cxcywh, gt_classes [G], pred_boxes [A,4], cls_logits [A,C],
+    obj_logits [A,1], shifts/strides [A].  Returns (fg_mask [A] bool,
+    matched_gt_inds [F], pred_ious [F], gt_matched_classes [F], num_fg).
+    """
+    G = gt_boxes.shape[0]
+    anchor_filter, ious, cost, _ = _simota_costs(gt_boxes, gt_classes, pred_boxes, cls_logits, obj_logits,
+                                                 x_shifts, y_shifts, strides, num_classes)
 
     # simota_matching, :542-574
     matching = torch.zeros_like(cost, dtype=torch.uint8)
-    n_cand = min(10, ious.size(1))
-    topk, _ = torch.topk(ious, n_cand, dim=1)
-    dyn_k = torch.clamp(topk.sum(1).int(), min=1)
+    _, dyn_k = _dynamic_k(ious)
     for g in range(G):
         _, pos = torch.topk(cost[g], k=int(dyn_k[g]), largest=False)
         matching[g][pos] = 1
@@ -330,6 +346,74 @@ def simota_assign(gt_boxes: Tensor, gt_classes: Tensor, pred_boxes: Tensor, cls_
     matched = matching[:, fg_in].argmax(0)
     pred_ious = (matching * ious).sum(0)[fg_in]
     return fg_mask, matched, pred_ious, gt_classes[matched], num_fg
+
+
+# An image is "rounding-decided" when one of simota_assign's discrete decisions hangs on the last
+# bits of a cost or an IoU sum, so that an implementation whose log / exp round differently may
+# decide otherwise without being wrong.  A cost is a sum of at most C + 4 <= 84 fp32 terms, each a
+# few ulp off: about 1e-5 relative, and 1e-4 leaves ten times that.  Ten IoUs of at most 1, each a
+# few ulp off, are about 1e-6 absolute off; 1e-3 is generous.
+MARGIN_TOPK_ABS = 1e-3
+MARGIN_COST_REL = 1e-4
+
+
+def _cost_gap(cost: Tensor, base: Tensor, lo: int, hi: int) -> float:
+    """Relative gap between two costs of one row/column, ``cost[lo] <= cost[hi]``.  Relative to
+    the cost WITHOUT its geometry term: that part carries the rounding error, while 1e6 is an
+    exact constant whose addition rounds the rest to 1/16.  Two such sums in neighbouring 1/16
+    bins count as gap 0 when one of them lies within the error of the rest from the edge of its
+    bin: elsewhere it may land in the next bin and tie."""
+    mag = max(abs(float(base[lo])), abs(float(base[hi])), 1e-30)
+    c_lo, c_hi = float(cost[lo]), float(cost[hi])
+    if c_lo >= 5e5:
+        ulp = float(np.spacing(np.float32(c_lo)))
+        if c_hi - c_lo <= ulp:
+            for i, c in ((lo, c_lo), (hi, c_hi)):
+                exact = float(base[i]) + 1e6  # float64: exact enough to place it inside its fp32 bin
+                if ulp / 2 - abs(exact - c) < MARGIN_COST_REL * mag:
+                    return 0.0
+    return (c_hi - c_lo) / mag
+
+
+def simota_margins(gt_boxes: Tensor, gt_classes: Tensor, pred_boxes: Tensor, cls_logits: Tensor,
+                   obj_logits: Tensor, x_shifts: Tensor, y_shifts: Tensor, strides: Tensor,
+                   num_classes: int = 80):
+    """How far ONE image's assignment (simota_assign, same arguments) is from deciding otherwise:
+      (a) min over ground truths of the distance from the top-k IoU sum to the nearest integer
+          boundary that changes dynamic_k (sums below 1 count their distance to 1);
+      (b) min over ground truths of the relative gap between the dynamic_k-th and the next cost;
+      (c) min, over the anchors claimed by more than one ground truth, of the relative gap
+          between the two lowest distinct costs of the anchor (equal costs come from identical
+          label rows: identical arithmetic, the first row wins everywhere -- a tie, not rounding).
+    A margin that does not apply (no next cost, no anchor claimed twice) is inf."""
+    G = gt_boxes.shape[0]
+    _, ious, cost, base = _simota_costs(gt_boxes, gt_classes, pred_boxes, cls_logits, obj_logits,
+                                        x_shifts, y_shifts, strides, num_classes)
+    sums, dyn_k = _dynamic_k(ious)
+    n = cost.shape[1]
+    a = b = c = float("inf")
+    claimed = torch.zeros(n, dtype=torch.int64)
+    for g in range(G):
+        s, k = float(sums[g]), int(dyn_k[g])
+        if s < 1.0:
+            a = min(a, 1.0 - s)
+        else:
+            a = min(a, min(abs(s - m) for m in (max(int(s), 2), int(s) + 1)))
+        order = torch.argsort(cost[g], stable=True)
+        claimed[order[:k]] += 1
+        if k < n:
+            b = min(b, _cost_gap(cost[g], base[g], int(order[k - 1]), int(order[k])))
+    for j in torch.nonzero(claimed > 1).flatten().tolist():
+        order = torch.argsort(cost[:, j], stable=True)
+        nxt = next((int(q) for q in order[1:] if float(cost[q, j]) != float(cost[order[0], j])), None)
+        if nxt is not None:
+            c = min(c, _cost_gap(cost[:, j], base[:, j], int(order[0]), nxt))
+    return a, b, c
+
+
+def rounding_decided(margins) -> bool:
+    a, b, c = margins
+    return a < MARGIN_TOPK_ABS or b < MARGIN_COST_REL or c < MARGIN_COST_REL
 
 
 # ----------------------------------------------------------------- training

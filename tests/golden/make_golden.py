@@ -21,6 +21,8 @@ Outputs (all under tests/golden/ unless stated):
   train_yolox_s_128.npz  train-mode forward: losses, per-image SimOTA assignment,
                          selected gradients (use_l1 False and True)
   simota_640.npz         get_assignments on synthetic 640 predictions, G=50
+  simota_edges.npz       get_assignments / get_losses on the edge batches of tests/simota_cases.py
+                         (`make_golden.py simota_edges`)
   boxes.npz              bboxes_iou (xyxy / cxcywh), IouLoss
   postprocess_pre_nms.npz  the (boxes, scores, idxs) the reference gives batched_nms
   cocoeval.npz           the reference's compiled COCO evaluator (oracle/_ref) on the synthetic
@@ -358,6 +360,53 @@ def gen_simota(ref) -> None:
     save("simota_640.npz", **arrays)
 
 
+def gen_simota_edges(ref) -> None:
+    """The reference's get_assignments (per image with labels) and get_losses (use_l1 off and on)
+    on every batch of tests/simota_cases.py: non-square, 1 / 3 / 20 / 80 classes, dynamic_k up to
+    9, saturated logits, duplicated / off-image / corner labels, empty images.  Inputs are
+    regenerated from seeds; stored are the labels, the reference's results and the oracle's
+    per-image rounding-decided flag (oracle.simota_margins)."""
+    sys.path.insert(0, REPO)
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import simota_cases as SC
+    from oracle import reference_cpu as O
+    arrays = {}
+    for name in SC.case_names():
+        c = SC.get_case(name)
+        head = ref.head.YoloxHead(c["C"], width=0.5)
+        x_s, y_s, st = (torch.from_numpy(a.copy())[None] for a in SC.anchors(c["H"], c["W"]))
+        outputs = torch.from_numpy(c["outputs"].copy())
+        lab = torch.from_numpy(c["labels"].copy())
+        origin = torch.from_numpy(c["origin"].copy())
+        arrays[f"{name}.labels"] = c["labels"]
+        flags = []
+        for b in range(outputs.shape[0]):
+            num_gt = int((lab[b].sum(1) > 0).sum())
+            if num_gt == 0:
+                flags.append(False)
+                continue
+            gt_cls, fg_mask, pred_ious, matched, num_fg = head.get_assignments(
+                b, num_gt, lab[b, :num_gt, 1:5], lab[b, :num_gt, 0], outputs[b, :, :4], st, x_s, y_s,
+                outputs[:, :, 5:], outputs[:, :, 4:5])
+            arrays[f"{name}.img{b}.fg_mask"] = fg_mask.numpy()
+            arrays[f"{name}.img{b}.matched_gt_inds"] = matched.numpy()
+            arrays[f"{name}.img{b}.pred_ious"] = pred_ious.numpy()
+            arrays[f"{name}.img{b}.num_fg"] = np.int64(num_fg)
+            flags.append(O.rounding_decided(O.simota_margins(
+                lab[b, :num_gt, 1:5], lab[b, :num_gt, 0], outputs[b, :, :4], outputs[b, :, 5:],
+                outputs[b, :, 4:5], x_s[0], y_s[0], st[0], c["C"])))
+        arrays[f"{name}.rounding"] = np.array(flags)
+        for use_l1 in (False, True):
+            head.use_l1 = use_l1
+            res = head.get_losses(None, [x_s], [y_s], [st], lab, outputs, [origin] if use_l1 else [],
+                                  torch.float32)
+            # get_losses order: total, iou, conf (obj), cls, l1, num_fg
+            arrays[f"{name}.{'l1' if use_l1 else 'nol1'}.losses"] = np.array(
+                [v.item() if torch.is_tensor(v) else v for v in res], np.float64)
+        print(f"simota_edges {name}: {int(np.sum(flags))} of {len(flags)} images rounding-decided")
+    save("simota_edges.npz", **arrays)
+
+
 def gen_boxes(ref) -> None:
     rng = np.random.default_rng(41)
     a = rng.uniform(0, 100, (13, 4)).astype(np.float32)
@@ -627,6 +676,7 @@ def main() -> None:
     gen_blocks(ref)
     gen_train(ref)
     gen_simota(ref)
+    gen_simota_edges(ref)
     gen_boxes(ref)
     gen_postprocess(ref)
     gen_processor(ref)

@@ -20,6 +20,7 @@ import torch
 import torch.nn.functional as F
 
 from conftest import GOLDEN
+from simota_cases import loss_bwd_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -640,30 +641,8 @@ def test_loss_bwd_matches_autograd(oracle, use_l1):
                                  assign["matched_gt_inds"].data_ptr(), assign["pred_ious"].data_ptr(), nfg.data_ptr(),
                                  gt.data_ptr(), int(use_l1), 0, g_ro.data_ptr(), g_cls.data_ptr(), stream()))
     torch.cuda.synchronize()
-    # autograd reference with the device's assignment as fixed targets
-    r = raw.clone().requires_grad_()
-    dec = torch.cat([(r[..., :2] + torch.stack([xs, ys], 1)) * st[:, None], torch.exp(r[..., 2:4]) * st[:, None],
-                     r[..., 4:]], -1)
-    fg = assign["fg_mask"].cpu().bool()
-    matched = assign["matched_gt_inds"].cpu().long()
-    piou = assign["pred_ious"].cpu()
-    num_fg = max(int(fg.sum()), 1)
-    tot = 0.0
-    for b in range(B):
-        f = fg[b]
-        gtb = labels[b][matched[b][f]]
-        tot = tot + 5.0 * oracle.iou_loss(dec[b, f, :4], gtb[:, 1:5]).sum()
-        tot = tot + F.binary_cross_entropy_with_logits(r[b, :, 4], f.float(), reduction="sum")
-        tgt = F.one_hot(gtb[:, 0].long(), nc).float() * piou[b][f][:, None]
-        tot = tot + F.binary_cross_entropy_with_logits(r[b, f, 5:], tgt, reduction="sum")
-        if use_l1:
-            s_ = st[f]
-            l1t = torch.stack([gtb[:, 1] / s_ - xs[f], gtb[:, 2] / s_ - ys[f], torch.log(gtb[:, 3] / s_ + 1e-8),
-                               torch.log(gtb[:, 4] / s_ + 1e-8)], 1)
-            tot = tot + (r[b, f, :4] - l1t).abs().sum()
-    (2.0 * tot / num_fg).backward()
-    ref = r.grad
-    assert float(losses["total_loss"]) == pytest.approx(float(tot) / num_fg, rel=1e-5)
+    ref, ref_total = loss_bwd_reference(oracle, raw, labels, xs, ys, st, assign, use_l1, 2.0)
+    assert float(losses["total_loss"]) == pytest.approx(ref_total, rel=1e-5)
     assert rel(g_ro[..., :5], ref[..., :5]) < 1e-5
     assert float(g_ro[..., 5:].abs().max()) == 0.0
     assert rel(g_cls, ref[..., 5:]) < 1e-5
