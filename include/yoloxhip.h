@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define YXH_ABI_VERSION 19
+#define YXH_ABI_VERSION 20
 
 enum yxh_status {
     YXH_OK = 0,
@@ -405,6 +405,25 @@ int yxh_postprocess_scored(float* pred, const float* scores, int32_t batch, int3
                            int32_t num_classes, float conf_thre, double nms_thre, int32_t class_agnostic,
                            int64_t vanilla_numel, float* det, int32_t* counts, void* workspace,
                            size_t workspace_bytes, void* filter_done, void* filter_stream, void* rest_stream);
+
+/*
+ * yxh_detections_pack (ABI 20): the serving pipeline's result records.  `det` [B, A, 7] fp32 and
+ * `counts` [B] int32 exactly as yxh_postprocess* leaves them; images at or beyond `n_valid` (<= B: a
+ * short last batch) count as 0 detections.  The detections of images 0 .. n_valid-1 are compacted, in
+ * image order then keep order, into 32-byte rows
+ *   { x1/r, y1/r, x2/r, y2/r, obj, cls_conf } fp32, label int32 (column 6 converted), image index int32
+ * with r = ratios[image], the letterbox ratio: YoloxProcessor.postprocess's formatting (processor.py:
+ * 39-54).  The division is the correctly rounded fp32 divide with denormals kept, which is what torch's
+ * CPU kernel computes for `boxes / ratio`, so the boxes are bit-identical to the reference's.
+ * offsets_out [B+1] int32: the exclusive prefix sum of the counts; offsets_out[B] is the total, also when
+ * it exceeds `capacity_rows` -- rows at or beyond `capacity_rows` are not written anywhere (a caller that
+ * sized rows_out for B * A rows loses nothing).  One launch: every block sums the counts in front of its
+ * image itself.  det and rows_out 16-byte aligned.  Bad arguments (null pointers, B <= 0, A <= 0,
+ * n_valid outside [0, B], negative capacity) return YXH_EINVAL before the runtime is touched.
+ */
+int yxh_detections_pack(const float* det, const int32_t* counts, int32_t batch, int32_t anchors,
+                        int32_t n_valid, const float* ratios, void* rows_out, int32_t capacity_rows,
+                        int32_t* offsets_out, void* stream);
 
 /*
  * yxh_yolox_loss: YoloxHead.get_losses (yolo_head.py:253-411) with SimOTA assignment

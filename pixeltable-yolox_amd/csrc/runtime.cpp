@@ -97,6 +97,8 @@ int head_pred_launch(const yxh_head_desc* d, hipStream_t st);
 int stem_s2_launch(const yxh_stem2_desc* d, hipStream_t st);
 int augment_batch_launch(const uint8_t* pool, const yxh_aug_image* images, int B, int H, int W, uint8_t* mosaic_ws,
                          float* out, hipStream_t st);
+int detections_pack_launch(const float* det, const int* counts, int B, int A, int n_valid, const float* ratios,
+                           void* rows_out, int capacity_rows, int* offsets_out, hipStream_t st);
 
 static int run_op(const yxh_op& op, hipStream_t st) {
     switch (op.kind) {
@@ -228,6 +230,13 @@ int yxh_postprocess_scored(float* pred, const float* scores, int32_t batch, int3
     return postprocess(pred, batch, anchors, num_classes, conf_thre, nms_thre, class_agnostic, vanilla_numel, det,
                        counts, workspace, workspace_bytes, (hipStream_t)filter_stream, (hipEvent_t)filter_done,
                        (hipStream_t)rest_stream, scores);
+}
+
+int yxh_detections_pack(const float* det, const int32_t* counts, int32_t batch, int32_t anchors, int32_t n_valid,
+                        const float* ratios, void* rows_out, int32_t capacity_rows, int32_t* offsets_out,
+                        void* stream) {
+    return detections_pack_launch(det, counts, batch, anchors, n_valid, ratios, rows_out, capacity_rows, offsets_out,
+                                  (hipStream_t)stream);
 }
 
 size_t yxh_yolox_loss_workspace_bytes(int32_t batch, int32_t anchors, int32_t max_labels) {

@@ -68,6 +68,34 @@ def _as_image_array(a: np.ndarray) -> np.ndarray:
     return a
 
 
+def letterbox_layout(arrays: list[np.ndarray], size: tuple[int, int]) -> tuple[list[np.ndarray], list[int], int]:
+    """Validate the images like the reference's preproc and lay them out in one pool: returns
+    (arrays, byte offset of each image, offset of the 16-byte descriptors behind them)."""
+    th, tw = int(size[0]), int(size[1])
+    arrays = [_as_image_array(a) for a in arrays]
+    for a in arrays:
+        r = min(th / a.shape[0], tw / a.shape[1])
+        if int(a.shape[1] * r) <= 0 or int(a.shape[0] * r) <= 0:
+            raise ValueError(f"image {a.shape[:2]} resizes to nothing at {size}")
+    offs, off = [], 0
+    for a in arrays:
+        offs.append(off)
+        off += (a.nbytes + 15) // 16 * 16
+    return arrays, offs, off
+
+
+def letterbox_fill(hn: np.ndarray, arrays: list[np.ndarray], offs: list[int], desc_off: int) -> None:
+    """Write the image bytes and their yxh_lb_image descriptors into the host pool ``hn`` (uint8)."""
+    B = len(arrays)
+    for a, o in zip(arrays, offs):
+        hn[o:o + a.nbytes] = a.reshape(-1) if a.flags.c_contiguous else np.ascontiguousarray(a).reshape(-1)
+    desc = np.zeros(B, dtype=[("off", "<i8"), ("h", "<i4"), ("w", "<i4")])
+    desc["off"] = offs
+    desc["h"] = [a.shape[0] for a in arrays]
+    desc["w"] = [a.shape[1] for a in arrays]
+    hn[desc_off:desc_off + 16 * B] = desc.view(np.uint8)
+
+
 def letterbox_batch(arrays: list[np.ndarray], size: tuple[int, int], out_format: str = "f32_nchw",
                     device=None) -> torch.Tensor:
     """uint8 HWC RGB arrays -> the letterboxed batch on the device, in one launch:
@@ -82,27 +110,11 @@ def letterbox_batch(arrays: list[np.ndarray], size: tuple[int, int], out_format:
     out = torch.empty(shape, dtype=dtype, device=device)
     if B == 0:
         return out
-    arrays = [_as_image_array(a) for a in arrays]
-    for a in arrays:
-        r = min(th / a.shape[0], tw / a.shape[1])
-        if int(a.shape[1] * r) <= 0 or int(a.shape[0] * r) <= 0:
-            raise ValueError(f"image {a.shape[:2]} resizes to nothing at {size}")
-    offs, off = [], 0
-    for a in arrays:
-        offs.append(off)
-        off += (a.nbytes + 15) // 16 * 16
-    desc_off = off
+    arrays, offs, desc_off = letterbox_layout(arrays, size)
     total = desc_off + 16 * B
     with _staging.lock:
         host = _staging.get(total)
-        hn = host.numpy()
-        for a, o in zip(arrays, offs):
-            hn[o:o + a.nbytes] = a.reshape(-1) if a.flags.c_contiguous else np.ascontiguousarray(a).reshape(-1)
-        desc = np.zeros(B, dtype=[("off", "<i8"), ("h", "<i4"), ("w", "<i4")])
-        desc["off"] = offs
-        desc["h"] = [a.shape[0] for a in arrays]
-        desc["w"] = [a.shape[1] for a in arrays]
-        hn[desc_off:total] = desc.view(np.uint8)
+        letterbox_fill(host.numpy(), arrays, offs, desc_off)
         dev = torch.empty(total, dtype=torch.uint8, device=device)
         dev.copy_(host[:total], non_blocking=True)
         _staging.event = torch.cuda.Event()

@@ -16,7 +16,7 @@ from __future__ import annotations
 
 import os
 from pathlib import Path
-from typing import Iterable, Optional, Union
+from typing import Iterable, Iterator, Optional, Union
 
 import torch
 import torch.nn as nn
@@ -252,6 +252,8 @@ class Yolox:
     def __init__(self, module: YoloxModule, processor: YoloxProcessor):
         self.module = module
         self.processor = processor
+        self._pipelines: dict = {}  # yolox_amd.serve.Pipeline per (device, dtype, batch size, test size)
+        self._streaming = False
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: Union[str, os.PathLike],
@@ -271,3 +273,40 @@ class Yolox:
         batch = self.processor.images_to_device(images, "u8_nhwc")
         output = self.module.forward_nhwc(batch)
         return self.processor.postprocess(images, output, threshold=threshold)
+
+    def pipeline(self, batch_size: int = 32, tune: bool = False):
+        """The serving pipeline ``stream`` runs batches of ``batch_size`` through (built on first use;
+        rebuilt after ``module.to(...)`` changed the device or dtype).  ``tune``: a pipeline built by
+        this call autotunes its plan's conv tiles first (engine.Plan.autotune)."""
+        from ..serve import Pipeline
+
+        m = self.module
+        size = tuple(int(v) for v in self.processor.config.test_size)
+        key = (str(m.device), m.compute_dtype, int(batch_size), size)
+        # module.to(...) changed the device or dtype: every pipeline built before is stale
+        self._pipelines = {k: p for k, p in self._pipelines.items() if k[:2] == key[:2] and p.module is m}
+        pipe = self._pipelines.get(key)
+        if pipe is None:
+            pipe = self._pipelines[key] = Pipeline(m, self.processor, batch_size, tune=tune)
+        return pipe
+
+    def stream(self, inputs: Iterable, threshold: float = 0.5, batch_size: int = 32) -> Iterator[Detections]:
+        """One ``Detections`` per input, in input order, from the pipelined serving path
+        (yolox_amd.serve.Pipeline): batches of ``batch_size`` go through a captured forward, the
+        device NMS and ``yxh_detections_pack`` while the host packs the next batch and formats the
+        last one.  ``inputs``: what ``__call__`` accepts (paths, PIL images) and H x W x 3 uint8 RGB
+        arrays, from any iterable -- it is read lazily, at most two batches ahead of the results.
+        An input the reference rejects (grayscale, RGBA, empty) raises ValueError when its batch is
+        packed.  One stream per ``Yolox`` at a time: a second concurrent one raises RuntimeError;
+        closing or exhausting the generator releases it."""
+        if self._streaming:
+            raise RuntimeError("this Yolox already has an active stream; exhaust or close it first")
+        self._streaming = True
+        try:
+            yield from self.pipeline(batch_size).run(inputs, threshold)
+        finally:
+            self._streaming = False
+
+    def detect(self, inputs: Iterable, threshold: float = 0.5, batch_size: int = 32) -> list[Detections]:
+        """``list(self.stream(...))``."""
+        return list(self.stream(inputs, threshold=threshold, batch_size=batch_size))

@@ -71,7 +71,8 @@ def postprocess_device(prediction: torch.Tensor, num_classes: int, conf_thre: fl
                        nms_thre: float = 0.45, class_agnostic: bool = False,
                        vanilla_numel: int = VANILLA_NUMEL_CPU, det: Optional[torch.Tensor] = None,
                        counts: Optional[torch.Tensor] = None, filter_done: Optional[torch.cuda.Event] = None,
-                       rest_stream: Optional[torch.cuda.Stream] = None, scores: Optional[torch.Tensor] = None):
+                       rest_stream: Optional[torch.cuda.Stream] = None, scores: Optional[torch.Tensor] = None,
+                       workspace: Optional["_Workspace"] = None):
     """Asynchronous form: returns (det [B, A, 7], counts [B] int32) on the device,
     nothing synchronised, on the current stream.  ``prediction`` (fp32, on device) becomes xyxy
     in place.  ``filter_done`` is recorded once ``prediction`` is no longer read (after the
@@ -80,7 +81,9 @@ def postprocess_device(prediction: torch.Tensor, num_classes: int, conf_thre: fl
     stream; the sort / mask / reduce passes run on ``rest_stream`` after it (yxh_postprocess_split),
     and det / counts are complete in that stream's order.  ``scores``: the [B, A, 8] serving records
     the forward that wrote ``prediction`` emitted (engine.Plan.enable_scores): the filter reads them
-    instead of the class columns (yxh_postprocess_scored, same results)."""
+    instead of the class columns (yxh_postprocess_scored, same results).  ``workspace``: a
+    ``_Workspace`` the caller owns, used instead of the shared per-device slots (a serving pipeline
+    keeps two of its own, so what other callers left in the shared ones never reaches it)."""
     N.require_device(prediction, "prediction")
     if prediction.dtype != torch.float32 or not prediction.is_contiguous():
         raise ValueError("prediction must be a contiguous float32 [B, A, 5+C] tensor")
@@ -100,7 +103,11 @@ def postprocess_device(prediction: torch.Tensor, num_classes: int, conf_thre: fl
         N.require_device(scores, "scores")
         if tuple(scores.shape) != (B, A, 8) or scores.dtype != torch.float32 or not scores.is_contiguous():
             raise ValueError(f"scores must be a contiguous float32 {(B, A, 8)} tensor")
-    ws = _workspace(dev, B, A, split=rest_stream is not None)
+    if workspace is not None:
+        ws = workspace
+        ws.acquire(dev, int(N.lib().yxh_postprocess_workspace_bytes(B, A)))
+    else:
+        ws = _workspace(dev, B, A, split=rest_stream is not None)
     buf = ws.buf
     try:
         if scores is not None:
