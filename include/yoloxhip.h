@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define YXH_ABI_VERSION 20
+#define YXH_ABI_VERSION 21
 
 enum yxh_status {
     YXH_OK = 0,
@@ -443,6 +443,45 @@ int yxh_yolox_loss(const float* preds, const float* origin, const float* labels,
                    float* pred_iou, int32_t* num_fg, float* losses, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/*
+ * IouLoss (losses.py:7-51), ABI 21.  loss_type selects the box loss:
+ *   YXH_IOU_LOSS_IOU   1 - iou^2
+ *   YXH_IOU_LOSS_GIOU  1 - clamp(iou - (area_c - area_u) / max(area_c, 1e-16), -1, 1)
+ * with iou = area_i / (area_u + 1e-16) in the reference's fp32 operation order.
+ *
+ * yxh_yolox_loss_ex: yxh_yolox_loss with the box loss of the foreground anchors chosen by
+ * iou_loss_type (head.iou_loss.loss_type); losses[1] then holds 5 * that term.  The SimOTA
+ * assignment, pred_iou and the class targets use the plain IoU whatever the type.
+ * yxh_yolox_loss is yxh_yolox_loss_ex with YXH_IOU_LOSS_IOU.
+ *
+ * yxh_iou_loss: IouLoss.forward on n box pairs.  pred, target: contiguous fp32 [n, 4]
+ * (cx, cy, w, h), 16-byte aligned (each row is one 16-byte load).  reduction:
+ *   YXH_REDUCE_NONE  out[n]
+ *   YXH_REDUCE_SUM   out[1], the sum of the n losses
+ *   YXH_REDUCE_MEAN  out[1], that sum divided by n in fp32
+ * Sum and mean are deterministic: per-block trees, then one block over the per-block
+ * partials in a fixed order (accumulated in fp64, rounded once; no atomics).  They need
+ * yxh_iou_loss_workspace_bytes(n) bytes of workspace (8-byte aligned); none may pass NULL.
+ * n == 0 returns YXH_OK without a launch and leaves out untouched.
+ *
+ * yxh_iou_loss_bwd: gradient of that call.  grad_out: [n] for YXH_REDUCE_NONE, one value
+ * for sum and mean (mean's 1/n is applied here).  Writes g_pred [n, 4] and, when g_target
+ * is not NULL, g_target [n, 4] (both 16-byte aligned).
+ * An unknown loss_type or reduction returns YXH_EINVAL.
+ */
+enum yxh_iou_loss_type { YXH_IOU_LOSS_IOU = 0, YXH_IOU_LOSS_GIOU = 1 };
+enum yxh_reduction { YXH_REDUCE_NONE = 0, YXH_REDUCE_SUM = 1, YXH_REDUCE_MEAN = 2 };
+int yxh_yolox_loss_ex(const float* preds, const float* origin, const float* labels, int32_t batch,
+                      int32_t anchors, int32_t num_classes, int32_t max_labels, const int32_t* level_hw,
+                      const int32_t* strides, int32_t nlevels, uint8_t* fg_mask, int32_t* matched_gt,
+                      float* pred_iou, int32_t* num_fg, float* losses, void* workspace,
+                      size_t workspace_bytes, void* stream, int32_t iou_loss_type);
+size_t yxh_iou_loss_workspace_bytes(int64_t n);
+int yxh_iou_loss(const float* pred, const float* target, int64_t n, int32_t loss_type, int32_t reduction,
+                 float* out, void* ws, size_t ws_bytes, void* stream);
+int yxh_iou_loss_bwd(const float* pred, const float* target, int64_t n, int32_t loss_type, int32_t reduction,
+                     const float* grad_out, float* g_pred, float* g_target /* nullable */, void* stream);
+
 /* ============================================================== training
  * The backward pass of YoloxModule (train mode): BaseConv = conv -> BatchNorm2d (batch
  * statistics) -> act, and its gradients.  Data gradients of convolutions run on
@@ -613,6 +652,13 @@ int yxh_yolox_loss_bwd(const float* preds, const float* raw, const float* labels
                        const int32_t* matched_gt, const float* pred_iou, const int32_t* num_fg,
                        const float* grad_total, int32_t use_l1, int32_t dtype, void* g_regobj, void* g_cls,
                        void* stream);
+/* ABI 21: the same with the box loss of yxh_yolox_loss_ex; yxh_yolox_loss_bwd is type YXH_IOU_LOSS_IOU */
+int yxh_yolox_loss_bwd_ex(const float* preds, const float* raw, const float* labels, int32_t batch,
+                          int32_t anchors, int32_t num_classes, int32_t max_labels, const int32_t* level_hw,
+                          const int32_t* strides, int32_t nlevels, const uint8_t* fg_mask,
+                          const int32_t* matched_gt, const float* pred_iou, const int32_t* num_fg,
+                          const float* grad_total, int32_t use_l1, int32_t dtype, void* g_regobj, void* g_cls,
+                          void* stream, int32_t iou_loss_type);
 
 /*
  * Plan execution.  A forward pass is a fixed list of ops (built once per model and

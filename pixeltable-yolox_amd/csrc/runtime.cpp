@@ -60,7 +60,12 @@ void pp_set_mask_budget(size_t bytes);
 size_t sim_workspace(int B, int A, int L);
 int yolox_loss(const float* preds, const float* origin, const float* labels, int B, int A, int C, int L,
                const int* lhw, const int* strides, int nlev, uint8_t* fg, int* matched, float* piou, int* num_fg,
-               float* losses, void* ws, size_t ws_bytes, hipStream_t st);
+               float* losses, int iou_type, void* ws, size_t ws_bytes, hipStream_t st);
+size_t iou_loss_workspace(long long n);
+int iou_loss_launch(const float* pred, const float* target, long long n, int type, int reduction, float* out, void* ws,
+                    size_t ws_bytes, hipStream_t st);
+int iou_loss_bwd_launch(const float* pred, const float* target, long long n, int type, int reduction,
+                        const float* grad_out, float* g_pred, float* g_target, hipStream_t st);
 int letterbox_batch_launch(const uint8_t* pool, const yxh_lb_image* images, int B, int th, int tw, int fmt,
                            void* dst, hipStream_t st);
 size_t reduce_workspace(int C);
@@ -88,8 +93,8 @@ int head_decode_train_launch(const float* raw, int B, int A, int C, const int* l
                              float* out, hipStream_t st);
 int yolox_loss_bwd(const float* preds, const float* raw, const float* labels, int B, int A, int C, int L,
                    const int* lhw, const int* strides, int nlev, const uint8_t* fg, const int* matched,
-                   const float* piou, const int* num_fg, const float* gtot, int use_l1, int dt, void* g_ro,
-                   void* g_cls, hipStream_t st);
+                   const float* piou, const int* num_fg, const float* gtot, int use_l1, int iou_type, int dt,
+                   void* g_ro, void* g_cls, hipStream_t st);
 int postprocess(float* pred, int B, int A, int C, float conf, double nms, int agnostic, long long vanilla_numel,
                 float* det, int* counts, void* ws, size_t ws_bytes, hipStream_t st, hipEvent_t filter_done,
                 hipStream_t rest, const float* scores = nullptr);
@@ -248,7 +253,30 @@ int yxh_yolox_loss(const float* preds, const float* origin, const float* labels,
                    int32_t nlevels, uint8_t* fg_mask, int32_t* matched_gt, float* pred_iou, int32_t* num_fg,
                    float* losses, void* workspace, size_t workspace_bytes, void* stream) {
     return yolox_loss(preds, origin, labels, batch, anchors, num_classes, max_labels, level_hw, strides, nlevels,
-                      fg_mask, matched_gt, pred_iou, num_fg, losses, workspace, workspace_bytes, (hipStream_t)stream);
+                      fg_mask, matched_gt, pred_iou, num_fg, losses, YXH_IOU_LOSS_IOU, workspace, workspace_bytes,
+                      (hipStream_t)stream);
+}
+
+int yxh_yolox_loss_ex(const float* preds, const float* origin, const float* labels, int32_t batch, int32_t anchors,
+                      int32_t num_classes, int32_t max_labels, const int32_t* level_hw, const int32_t* strides,
+                      int32_t nlevels, uint8_t* fg_mask, int32_t* matched_gt, float* pred_iou, int32_t* num_fg,
+                      float* losses, void* workspace, size_t workspace_bytes, void* stream, int32_t iou_loss_type) {
+    return yolox_loss(preds, origin, labels, batch, anchors, num_classes, max_labels, level_hw, strides, nlevels,
+                      fg_mask, matched_gt, pred_iou, num_fg, losses, iou_loss_type, workspace, workspace_bytes,
+                      (hipStream_t)stream);
+}
+
+size_t yxh_iou_loss_workspace_bytes(int64_t n) { return iou_loss_workspace(n); }
+
+int yxh_iou_loss(const float* pred, const float* target, int64_t n, int32_t loss_type, int32_t reduction, float* out,
+                 void* ws, size_t ws_bytes, void* stream) {
+    return iou_loss_launch(pred, target, n, loss_type, reduction, out, ws, ws_bytes, (hipStream_t)stream);
+}
+
+int yxh_iou_loss_bwd(const float* pred, const float* target, int64_t n, int32_t loss_type, int32_t reduction,
+                     const float* grad_out, float* g_pred, float* g_target, void* stream) {
+    return iou_loss_bwd_launch(pred, target, n, loss_type, reduction, grad_out, g_pred, g_target,
+                               (hipStream_t)stream);
 }
 
 size_t yxh_reduce_workspace_bytes(int32_t channels) { return reduce_workspace(channels); }
@@ -333,8 +361,18 @@ int yxh_yolox_loss_bwd(const float* preds, const float* raw, const float* labels
                        const int32_t* num_fg, const float* grad_total, int32_t use_l1, int32_t dtype, void* g_regobj,
                        void* g_cls, void* stream) {
     return yolox_loss_bwd(preds, raw, labels, batch, anchors, num_classes, max_labels, level_hw, strides, nlevels,
-                          fg_mask, matched_gt, pred_iou, num_fg, grad_total, use_l1, dtype, g_regobj, g_cls,
-                          (hipStream_t)stream);
+                          fg_mask, matched_gt, pred_iou, num_fg, grad_total, use_l1, YXH_IOU_LOSS_IOU, dtype, g_regobj,
+                          g_cls, (hipStream_t)stream);
+}
+
+int yxh_yolox_loss_bwd_ex(const float* preds, const float* raw, const float* labels, int32_t batch, int32_t anchors,
+                          int32_t num_classes, int32_t max_labels, const int32_t* level_hw, const int32_t* strides,
+                          int32_t nlevels, const uint8_t* fg_mask, const int32_t* matched_gt, const float* pred_iou,
+                          const int32_t* num_fg, const float* grad_total, int32_t use_l1, int32_t dtype,
+                          void* g_regobj, void* g_cls, void* stream, int32_t iou_loss_type) {
+    return yolox_loss_bwd(preds, raw, labels, batch, anchors, num_classes, max_labels, level_hw, strides, nlevels,
+                          fg_mask, matched_gt, pred_iou, num_fg, grad_total, use_l1, iou_loss_type, dtype, g_regobj,
+                          g_cls, (hipStream_t)stream);
 }
 
 int yxh_run_ops(const yxh_op* ops, int32_t n, void* stream) {

@@ -16,11 +16,13 @@
 //                    the dynamic_k smallest costs (ties -> lower candidate index).
 //   sim_resolve    : per candidate.  Anchors matched by >1 GT keep the first argmin
 //                    cost over all GTs; fg mask, matched GT, pred IoU, num_fg.
-//   sim_loss       : per anchor partial sums (IoU^2 loss on fg, BCE-with-logits obj on
-//                    all, cls on fg with target onehot * IoU, optional L1), reduced in a
-//                    fixed order (deterministic), divided by max(sum num_fg, 1).
+//   sim_loss       : per anchor partial sums (IouLoss on fg, iou or giou: iou_loss.hpp;
+//                    BCE-with-logits obj on all, cls on fg with target onehot * IoU,
+//                    optional L1), reduced in a fixed order (deterministic), divided by
+//                    max(sum num_fg, 1).
 #pragma clang fp contract(off)  // IoU / cost formulas round like torch's separate ops
 
+#include "iou_loss.hpp"
 #include "yxh_common.hpp"
 
 namespace yxh {
@@ -291,7 +293,9 @@ __device__ __forceinline__ float bce_logits(float x, float t) {
     return (1.0f - t) * x + m + logf(expf(-m) + expf(-x - m));
 }
 
-// partial[b][blk][4] = (iou, obj, cls, l1) sums over this block's anchors
+// partial[b][blk][4] = (iou, obj, cls, l1) sums over this block's anchors; IOU_TYPE picks the
+// box loss (iou_loss.hpp), the class target stays the plain IoU of the assignment (piou)
+template <int IOU_TYPE>
 __global__ __launch_bounds__(256) void sim_loss(const float* preds, const float* origin, const float* labels,
                                                  int A, int C, int L, SimGeom geo, const uint8_t* fg,
                                                  const int* matched, const float* piou, float* partial) {
@@ -307,15 +311,7 @@ __global__ __launch_bounds__(256) void sim_loss(const float* preds, const float*
         if (f) {
             const int g = matched[(long long)b * A + a];
             const float* gt = labels + ((long long)b * L + g) * 5;
-            const float tlx = fmaxf(p[0] - p[2] / 2, gt[1] - gt[3] / 2);
-            const float tly = fmaxf(p[1] - p[3] / 2, gt[2] - gt[4] / 2);
-            const float brx = fminf(p[0] + p[2] / 2, gt[1] + gt[3] / 2);
-            const float bry = fminf(p[1] + p[3] / 2, gt[2] + gt[4] / 2);
-            const float area_p = p[2] * p[3], area_g = gt[3] * gt[4];
-            const float en = (tlx < brx && tly < bry) ? 1.0f : 0.0f;
-            const float area_i = ((brx - tlx) * (bry - tly)) * en;
-            const float io = area_i / (((area_p + area_g) - area_i) + 1e-16f);
-            li = 1.0f - io * io;
+            li = iou_loss_pair<IOU_TYPE>(p, gt + 1);
             const int k = (int)gt[0];
             const float t = piou[(long long)b * A + a];
             for (int c = 0; c < C; ++c) lc += bce_logits(p[5 + c], c == k ? t : 0.0f);
@@ -381,17 +377,11 @@ __global__ __launch_bounds__(256) void head_decode_train(const float* raw, int B
     out[idx] = v;
 }
 
-__device__ __forceinline__ float tie_w(float a, float b, bool want_greater) {
-    // torch.maximum / minimum backward: full gradient to the selected input, half on ties
-    if (a == b) return 0.5f;
-    return (want_greater ? a > b : a < b) ? 1.0f : 0.0f;
-}
-
 __device__ __forceinline__ float sgn(float v) { return v > 0.0f ? 1.0f : (v < 0.0f ? -1.0f : 0.0f); }
 
 // d total_loss / d raw outputs (autograd of yolo_head.py:382-402 + losses.py:13-51 through
 // the decode of :227-230); one thread per anchor.
-template <typename T>
+template <typename T, int IOU_TYPE>
 __global__ __launch_bounds__(256) void sim_loss_bwd(const float* preds, const float* raw, const float* labels, int B,
                                                     int A, int C, int L, SimGeom geo, const uint8_t* fg,
                                                     const int* matched, const float* piou, const int* num_fg,
@@ -417,27 +407,10 @@ __global__ __launch_bounds__(256) void sim_loss_bwd(const float* preds, const fl
         const int k = (int)gt[0];
         const float t = piou[row];
         for (int c = 0; c < C; ++c) gc[c] = from_f32<T>((sig(r[5 + c]) - (c == k ? t : 0.0f)) * gs);
-        // IoU loss (reg_weight 5): L = 1 - iou^2
-        const float px = p[0], py = p[1], pw = p[2], ph = p[3];
-        const float atx = px - pw / 2, btx = gt[1] - gt[3] / 2, aty = py - ph / 2, bty = gt[2] - gt[4] / 2;
-        const float abx = px + pw / 2, bbx = gt[1] + gt[3] / 2, aby = py + ph / 2, bby = gt[2] + gt[4] / 2;
-        const float tlx = fmaxf(atx, btx), tly = fmaxf(aty, bty), brx = fminf(abx, bbx), bry = fminf(aby, bby);
-        const float en = (tlx < brx && tly < bry) ? 1.0f : 0.0f;
-        const float dxx = brx - tlx, dyy = bry - tly;
-        const float ai = (dxx * dyy) * en;
-        const float ap = pw * ph, ag = gt[3] * gt[4];
-        const float u = ((ap + ag) - ai) + 1e-16f;
-        const float io = ai / u;
-        const float gi = 5.0f * gs * (-2.0f * io);
-        const float gu = -gi * ai / (u * u);
-        const float gai = gi / u - gu;
-        const float gap = gu;
-        const float gdx = gai * en * dyy, gdy = gai * en * dxx;
-        const float gtlx = -gdx * tie_w(atx, btx, true), gbrx = gdx * tie_w(abx, bbx, false);
-        const float gtly = -gdy * tie_w(aty, bty, true), gbry = gdy * tie_w(aby, bby, false);
-        const float gpx = gtlx + gbrx, gpy = gtly + gbry;
-        const float gpw = 0.5f * (gbrx - gtlx) + gap * ph;
-        const float gph = 0.5f * (gbry - gtly) + gap * pw;
+        // IouLoss (reg_weight 5) of the decoded box against its GT
+        float gp[4];
+        iou_loss_pair_bwd<IOU_TYPE, false>(p, gt + 1, 5.0f * gs, gp, nullptr);
+        const float gpx = gp[0], gpy = gp[1], gpw = gp[2], gph = gp[3];
         float xs, ys, st;
         anchor_geom(geo, a, xs, ys, st);
         gr[0] = gpx * st;
@@ -486,7 +459,9 @@ size_t sim_workspace(int B, int A, int L) {
 
 int yolox_loss(const float* preds, const float* origin, const float* labels, int B, int A, int C, int L,
                const int* lhw, const int* strides, int nlev, uint8_t* fg, int* matched, float* piou, int* num_fg,
-               float* losses, void* ws, size_t ws_bytes, hipStream_t st) {
+               float* losses, int iou_type, void* ws, size_t ws_bytes, hipStream_t st) {
+    YXH_CHECK_ARG(iou_type == YXH_IOU_LOSS_IOU || iou_type == YXH_IOU_LOSS_GIOU, "yolox_loss: iou_loss_type %d",
+                  iou_type);
     YXH_CHECK_ARG(preds && labels && fg && matched && piou && num_fg && losses && lhw && strides, "null pointer");
     YXH_CHECK_ARG(B > 0 && A > 0 && C > 0 && L > 0 && nlev > 0 && nlev <= 4, "shape B=%d A=%d C=%d L=%d", B, A, C, L);
     YXH_CHECK_ARG(ws && ws_bytes >= sim_workspace(B, A, L), "workspace too small");
@@ -523,8 +498,12 @@ int yolox_loss(const float* preds, const float* origin, const float* labels, int
     hipLaunchKernelGGL(sim_resolve, dim3((A + 255) / 256, B), dim3(256), 0, st, labels, A, L, w, fg, matched, piou,
                        num_fg);
     YXH_CHECK_LAUNCH("sim_resolve");
-    hipLaunchKernelGGL(sim_loss, dim3(nblk, B), dim3(256), 0, st, preds, origin, labels, A, C, L, geo, fg, matched,
-                       piou, w.partial);
+    if (iou_type == YXH_IOU_LOSS_GIOU)
+        hipLaunchKernelGGL(sim_loss<YXH_IOU_LOSS_GIOU>, dim3(nblk, B), dim3(256), 0, st, preds, origin, labels, A, C, L,
+                           geo, fg, matched, piou, w.partial);
+    else
+        hipLaunchKernelGGL(sim_loss<YXH_IOU_LOSS_IOU>, dim3(nblk, B), dim3(256), 0, st, preds, origin, labels, A, C, L,
+                           geo, fg, matched, piou, w.partial);
     YXH_CHECK_LAUNCH("sim_loss");
     hipLaunchKernelGGL(sim_finalize, dim3(1), dim3(64), 0, st, w.partial, B * nblk, num_fg, labels, B, L,
                        origin ? 1 : 0, losses);
@@ -548,17 +527,24 @@ int head_decode_train_launch(const float* raw, int B, int A, int C, const int* l
 
 int yolox_loss_bwd(const float* preds, const float* raw, const float* labels, int B, int A, int C, int L,
                    const int* lhw, const int* strides, int nlev, const uint8_t* fg, const int* matched,
-                   const float* piou, const int* num_fg, const float* gtot, int use_l1, int dt, void* g_ro,
-                   void* g_cls, hipStream_t st) {
+                   const float* piou, const int* num_fg, const float* gtot, int use_l1, int iou_type, int dt,
+                   void* g_ro, void* g_cls, hipStream_t st) {
+    YXH_CHECK_ARG(iou_type == YXH_IOU_LOSS_IOU || iou_type == YXH_IOU_LOSS_GIOU, "yolox_loss_bwd: iou_loss_type %d",
+                  iou_type);
     YXH_CHECK_ARG(preds && raw && labels && fg && matched && piou && num_fg && gtot && g_ro && g_cls && lhw && strides,
                   "null pointer");
     YXH_CHECK_ARG(B > 0 && A > 0 && C > 0 && L > 0 && nlev > 0 && nlev <= 4, "shape");
     SimGeom geo = make_geom(lhw, strides, nlev);
     YXH_CHECK_ARG(geo.off[nlev] == A, "level sizes sum to %d, not A=%d", geo.off[nlev], A);
     dim3 grid((A + 255) / 256, B);
-#define YXH_LB(T)                                                                                                    \
-    hipLaunchKernelGGL(sim_loss_bwd<T>, grid, dim3(256), 0, st, preds, raw, labels, B, A, C, L, geo, fg, matched,  \
-                       piou, num_fg, gtot, use_l1, (T*)g_ro, (T*)g_cls)
+#define YXH_LB1(T, K)                                                                                         \
+    hipLaunchKernelGGL((sim_loss_bwd<T, K>), grid, dim3(256), 0, st, preds, raw, labels, B, A, C, L, geo, fg, \
+                       matched, piou, num_fg, gtot, use_l1, (T*)g_ro, (T*)g_cls)
+#define YXH_LB(T)                                                         \
+    do {                                                                  \
+        if (iou_type == YXH_IOU_LOSS_GIOU) YXH_LB1(T, YXH_IOU_LOSS_GIOU); \
+        else YXH_LB1(T, YXH_IOU_LOSS_IOU);                                \
+    } while (0)
     if (dt == YXH_BF16) YXH_LB(bf16);
     else if (dt == YXH_F16) YXH_LB(f16);
     else if (dt == YXH_F32) YXH_LB(float);
@@ -567,6 +553,7 @@ int yolox_loss_bwd(const float* preds, const float* raw, const float* labels, in
         return YXH_EINVAL;
     }
 #undef YXH_LB
+#undef YXH_LB1
     YXH_CHECK_LAUNCH("sim_loss_bwd");
     return YXH_OK;
 }

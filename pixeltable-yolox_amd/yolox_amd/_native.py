@@ -17,7 +17,7 @@ import torch  # noqa: F401  (must precede loading the HIP library)
 LIB_PATH = os.environ.get(
     "YOLOX_AMD_LIB", os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "libyoloxhip.so"))
 
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 # enums (yoloxhip.h)
 OK, EINVAL, EHIP, EUNSUPPORTED = 0, -1, -2, -3
@@ -26,6 +26,10 @@ ACT_NONE, ACT_SILU, ACT_RELU, ACT_LRELU, ACT_DECODE, ACT_DECODE_TRAIN, ACT_DECOD
 NCHW, NHWC = 0, 1
 OP_CONV, OP_FOCUS, OP_SPP, OP_STEM, OP_HEAD, OP_STEM2 = 0, 1, 2, 3, 4, 5
 LB_F32_NCHW, LB_U8_NHWC, LB_BF16_NHWC = 0, 1, 2
+IOU_LOSS_IOU, IOU_LOSS_GIOU = 0, 1
+REDUCE_NONE, REDUCE_SUM, REDUCE_MEAN = 0, 1, 2
+IOU_LOSS_CODE = {"iou": IOU_LOSS_IOU, "giou": IOU_LOSS_GIOU}
+REDUCTION_CODE = {"none": REDUCE_NONE, "sum": REDUCE_SUM, "mean": REDUCE_MEAN}
 
 TORCH_DTYPE = {F32: torch.float32, BF16: torch.bfloat16, F16: torch.float16, U8: torch.uint8}
 DTYPE_CODE = {v: k for k, v in TORCH_DTYPE.items()}
@@ -216,6 +220,11 @@ def lib():
             "yxh_yolox_loss_workspace_bytes": ([i32, i32, i32], sz),
             "yxh_yolox_loss": ([vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp],
                                C.c_int),
+            "yxh_yolox_loss_ex": ([vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, vp, sz, vp, i32],
+                                  C.c_int),
+            "yxh_iou_loss_workspace_bytes": ([i64], sz),
+            "yxh_iou_loss": ([vp, vp, i64, i32, i32, vp, vp, sz, vp], C.c_int),
+            "yxh_iou_loss_bwd": ([vp, vp, i64, i32, i32, vp, vp, vp, vp], C.c_int),
             "yxh_reduce_workspace_bytes": ([i32], sz),
             "yxh_bn_stats": ([i32, i32, C.POINTER(Src), vp, vp, vp, vp, f32, f32, vp, vp, sz, vp], C.c_int),
             "yxh_bn_act_fwd": ([i32, i32, C.POINTER(Src), vp, i32, C.POINTER(Src), C.POINTER(Src), vp], C.c_int),
@@ -237,6 +246,8 @@ def lib():
             "yxh_head_decode_train": ([vp, i32, i32, i32, vp, vp, i32, vp, vp], C.c_int),
             "yxh_yolox_loss_bwd": ([vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp,
                                     vp, vp], C.c_int),
+            "yxh_yolox_loss_bwd_ex": ([vp, vp, vp, i32, i32, i32, i32, vp, vp, i32, vp, vp, vp, vp, vp, i32, i32, vp,
+                                       vp, vp, i32], C.c_int),
             "yxh_opt_chunk_elems": ([], C.c_int),
             "yxh_sgd_ema_step": ([vp, vp, i32, C.POINTER(OptHparams), vp], C.c_int),
             "yxh_amp_found_inf": ([vp, vp, i32, vp, vp], C.c_int),
@@ -272,6 +283,7 @@ EXPORTED = ["yxh_abi_version", "yxh_last_error", "yxh_sizeof_op", "yxh_sizeof_co
             "yxh_bn_act_bwd", "yxh_channel_sum", "yxh_conv_wgrad", "yxh_pack_dgrad_weight", "yxh_pack_weights_batch", "yxh_pack_frag", "yxh_spp_bwd",
             "yxh_upsample_bwd", "yxh_dw_wgrad_workspace_bytes", "yxh_dw_wgrad", "yxh_dw_dgrad", "yxh_resize_bilinear",
             "yxh_head_decode_train", "yxh_yolox_loss_bwd", "yxh_opt_chunk_elems",
+            "yxh_yolox_loss_ex", "yxh_yolox_loss_bwd_ex", "yxh_iou_loss_workspace_bytes", "yxh_iou_loss", "yxh_iou_loss_bwd",
             "yxh_sgd_ema_step", "yxh_amp_found_inf", "yxh_amp_update_scale", "yxh_coco_eval", "yxh_coco_iou"]
 
 

@@ -15,6 +15,8 @@ from typing import Sequence
 import torch
 import torch.nn as nn
 
+from .losses import IouLoss
+
 
 def _act_module(name: str) -> nn.Module:
     # network_blocks.py:15-24
@@ -459,6 +461,7 @@ class YoloxHead(_Planned):
             self.reg_preds.append(nn.Conv2d(hw_, 4, 1, 1, 0))
             self.obj_preds.append(nn.Conv2d(hw_, 1, 1, 1, 0))
         self.use_l1 = False
+        self.iou_loss = IouLoss(reduction="none")  # yolo_head.py:125; no parameters, no state_dict keys
         self.strides = list(strides)
 
     def forward(self, xin, labels=None, imgs=None):

@@ -36,7 +36,7 @@ import torch.nn as nn
 
 from . import _native as N
 from . import tiles as T
-from .models.losses import LOSS_KEYS
+from .models.losses import LOSS_KEYS, IouLoss
 from .models.network import (BaseConv, Bottleneck, CspDarknet, CspLayer, DWConv, Focus, SPPBottleneck,
                              YoloPafpn, YoloxHead)
 
@@ -675,6 +675,12 @@ class TrainGraph:
                                                  self.stream), "decode")
         L = labels.shape[1]
         use_l1 = bool(head.use_l1)
+        iou_loss = getattr(head, "iou_loss", None)
+        if not isinstance(iou_loss, IouLoss) or iou_loss.reduction != "none":
+            # get_losses sums the per-box values itself (yolo_head.py:383-385): no other reduction means anything
+            raise ValueError("head.iou_loss must be an IouLoss with reduction='none' "
+                             f"(got {iou_loss!r})")
+        iou_type = N.IOU_LOSS_CODE[iou_loss.loss_type]
         origin = raw[..., :4].contiguous() if use_l1 else None
         fg = torch.empty(B, A, dtype=torch.uint8, device=self.device)
         matched = torch.empty(B, A, dtype=torch.int32, device=self.device)
@@ -683,20 +689,20 @@ class TrainGraph:
         losses = torch.empty(6, dtype=torch.float32, device=self.device)
         ws = torch.empty(int(self.lib.yxh_yolox_loss_workspace_bytes(B, A, L)), dtype=torch.uint8,
                          device=self.device)
-        self._chk(self.lib.yxh_yolox_loss(
+        self._chk(self.lib.yxh_yolox_loss_ex(
             preds.data_ptr(), origin.data_ptr() if origin is not None else None, labels.data_ptr(), B, A, nc, L,
             lhw, strides, len(hw), fg.data_ptr(), matched.data_ptr(), piou.data_ptr(), num_fg.data_ptr(),
-            losses.data_ptr(), ws.data_ptr(), ws.numel(), self.stream), "yolox loss")
+            losses.data_ptr(), ws.data_ptr(), ws.numel(), self.stream, iou_type), "yolox loss")
         self.assign = {"fg_mask": fg, "matched_gt_inds": matched, "pred_ious": piou, "num_fg": num_fg}
         self.outputs = preds
 
         def backward():
             g_ro = torch.empty(B, A, 8, dtype=self.dtype, device=self.device)
             g_cls = torch.empty(B, A, nc, dtype=self.dtype, device=self.device)
-            self._chk(self.lib.yxh_yolox_loss_bwd(
+            self._chk(self.lib.yxh_yolox_loss_bwd_ex(
                 preds.data_ptr(), raw.data_ptr(), labels.data_ptr(), B, A, nc, L, lhw, strides, len(hw),
                 fg.data_ptr(), matched.data_ptr(), piou.data_ptr(), num_fg.data_ptr(), self.grad_total.data_ptr(),
-                int(use_l1), self.dcode, g_ro.data_ptr(), g_cls.data_ptr(), self.stream), "loss bwd")
+                int(use_l1), self.dcode, g_ro.data_ptr(), g_cls.data_ptr(), self.stream, iou_type), "loss bwd")
             gb = self.grads
             for k, r, c, w_ro, a0, h, w in reversed(levels):
                 for g_all, ch, feat, wmat, convs in (
@@ -798,6 +804,10 @@ class CapturedTrainStep:
     segment's stream (the eager step's exact event placement: the reducer's bucketed RCCL
     all-reduces are issued between segments, overlapping the later segments), and finishes the
     reducer behind the last segment (1/world mean on the compute stream), as the eager backward does.
+
+    The graph holds the loss kernels the capture launched: like ``head.use_l1``, the box loss type
+    (``head.iou_loss.loss_type``, iou or giou) is the one the head had at capture; changing either
+    afterwards needs a new capture.
 
     Requirements: the step ran eagerly once for this shape (tiles tuned, the repack table
     recorded), and the parameters keep their storage (``model.to`` / re-created tensors need a new
