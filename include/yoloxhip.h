@@ -534,14 +534,22 @@ typedef struct {
     yxh_src src[2];
     yxh_src dy;
     float* dw;
-    int32_t tile, reserved;  /* tile 0: by shape; 17-20 (fp32, any kernel / stride): k-major MFMA operands,
-                                one tap per block, 64x64, 128x128,
-                                128x64, 64x128; 1-4: 64x64, 128x128, 32x64, 16x64 (cout x cin,
-                                register-transposed loader); 5-10 (bf16/f16): LDS-DMA +
-                                ds_read_b64_tr_b16, 128x128 (3 / 2 buffers), 64x64 (3 / 2),
-                                128x64, 64x128 */
-    /* fp32 tiles 17-20: optional scratch for per-split partial gradients; with it the splits are
-     * summed by a second launch in a fixed order (deterministic, no atomics) */
+    /* tile 0: by shape (one of 1-4).  Tiles are cout x cin; a tile outside its family's operand types
+     * or conv shape returns YXH_EUNSUPPORTED, an id in no family YXH_EINVAL.
+     *   1-4   (any type, any conv): register-transposed loader, one tap per block: 64x64, 128x128, 32x64, 16x64
+     *   5-10  (bf16/f16, any conv): LDS-DMA + ds_read_b64_tr_b16: 128x128 (3 / 2 buffers), 64x64 (3 / 2),
+     *         128x64, 64x128
+     *   11-16 (fp32, 3x3 pad 1 stride 1/2, one plain source): all nine taps per block over LDS-transposed
+     *         pixel tiles: 32x32, 64x32, 64x64, 32x16, 32x32 (half the rows per tile), 64x16
+     *   17-20 (fp32, any conv): k-major MFMA operands, one tap per block: 64x64, 128x128, 128x64, 64x128
+     *   21-24 (fp32, 3x3 pad 1 stride 1/2): k-major operands, all nine taps per block: 64x64, 64x64
+     *         (32 / 8 pixels per stage at stride 1 / 2), 32x64, 64x32
+     *   25-30 (bf16/f16, 3x3 pad 1 stride 1/2): nine taps per block, transposed LDS reads: 64x64, 128x64,
+     *         64x128 (stride 1 only), 64x64 (64 pixels per stage), 160x32, 32x160 */
+    int32_t tile, reserved;
+    /* optional scratch for per-split partial gradients, honoured by every tile: with it the splits are
+     * summed by a second launch in a fixed order (deterministic, no atomics).  A launch uses at most
+     * 16 MiB of it (tiles 25-30: 64 MiB); a scratch too small for one partial is ignored (atomics). */
     float* workspace;
     int64_t workspace_bytes;
 } yxh_wgrad_desc;

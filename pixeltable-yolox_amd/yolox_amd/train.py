@@ -41,7 +41,7 @@ from .models.network import (BaseConv, Bottleneck, CspDarknet, CspLayer, DWConv,
                              YoloPafpn, YoloxHead)
 
 MAX_CHANNELS = 4096  # reduction workspace sizing (yolox_x: 1280)
-WGRAD_WS_BYTES = 64 << 20  # = the launchers' largest cap on per-split partials (16 Mi floats, tiles 25-28)
+WGRAD_WS_BYTES = 64 << 20  # = the launchers' largest cap on per-split partials (16 Mi floats, tiles 25-30)
 DW_WS_BYTES = 16 << 20  # depthwise weight-gradient partials per stream (yolox_nano 640 batch 64: < 1 MiB)
 
 
@@ -197,9 +197,9 @@ class TrainGraph:
         # weight gradients run on a side stream beside the data-gradient chain (YOLOX_AMD_WGRAD_STREAM=0: inline)
         self._wside = (torch.cuda.Stream(self.device) if os.environ.get("YOLOX_AMD_WGRAD_STREAM", "1") != "0"
                        and self.device.type == "cuda" else None)
-        # per-split partial weight gradients of the fp32 wgrad tiles (summed in a fixed order); the
-        # launcher uses at most 16 MiB of partials, 64 MiB for the 16-bit nine-tap tiles 25-28
-        # (csrc/train.hip ws_cap_splits; a weight too large
+        # per-split partial weight gradients of every wgrad tile (summed in a fixed order); the
+        # launcher uses at most 16 MiB of partials, 64 MiB for the 16-bit nine-tap tiles 25-30
+        # (csrc/wgrad.hpp ws_cap_splits; a weight too large
         # for one split falls back to fp32 atomics).  One workspace per stream that issues
         # weight gradients (head preds: main stream; BaseConvs: the side stream), so work in
         # flight on one stream never shares partials with the other.
