@@ -1,13 +1,18 @@
 """``yolox train`` (reference yolox/cli/train.py:19-143 + cli/utils.py) on the HIP path.
 
-    python -m yolox_amd train -c yolox-s -d 8 -b 64 --fp16 [-o] [-D key=value ...]
+    python -m yolox_amd train -c yolox-s -d 8 -b 64 --fp16 [-o] [--resume] [--ckpt FILE] [-e N]
+                              [-D key=value ...]
 
 Same flags and meaning as the reference: ``-c`` a named config (or ``module:Class``),
 ``-d`` processes = GPUs of this machine (one process per GPU, yolox_amd.launch), ``-b`` the
 GLOBAL batch (each rank trains on b / d images), ``--fp16`` mixed precision through
-autocast + GradScaler, ``-D`` config overrides.  Added: ``--max-iter`` (stop after that
-many iterations) and ``--dataset-size`` (length of the synthetic COCO-shaped dataset that
-stands in for COCO offline).  Loggers, checkpoint resume and evaluation are out of scope.
+autocast + GradScaler, ``-D`` config overrides, ``--resume`` continue from ``--ckpt`` or
+``<output_dir>/<name>/latest_ckpt.pth`` (``-e`` overrides the epoch to start at, 1-based),
+``--ckpt`` alone fine-tune from a checkpoint's matching weights.  Every epoch end writes
+checkpoints there and, with an evaluation dataset (``YoloxConfig.get_eval_dataset`` of a
+``module:Class`` config), evaluates (yolox_amd.trainer).  Added: ``--max-iter`` (stop after
+that many iterations) and ``--dataset-size`` (length of the synthetic COCO-shaped dataset
+that stands in for COCO offline).  Loggers and ``--cache`` are out of scope.
 """
 from __future__ import annotations
 
@@ -85,13 +90,18 @@ def train(config: YoloxConfig, args) -> None:
     trainer.train()
 
 
+def check_args(args) -> None:
+    """The argument errors of cli/train.py:118-119 plus what this path does not build."""
+    if args.config is None:
+        raise AttributeError("Please specify a model configuration.")
+    if args.cache:
+        raise NotImplementedError("--cache: dataset caches are out of scope")
+
+
 def main(argv: list) -> None:
     """cli/train.py:116-143: resolve and validate the config, then one process per GPU."""
     args = make_parser().parse_args(argv)
-    if args.config is None:
-        raise AttributeError("Please specify a model configuration.")
-    if args.resume or args.ckpt or args.cache:
-        raise NotImplementedError("--resume / --ckpt / --cache: checkpoint files and dataset caches are out of scope")
+    check_args(args)
     config = resolve_config(args.config)
     config.update(parse_model_config_opts(args.D))
     config.validate()
@@ -108,5 +118,6 @@ def main(argv: list) -> None:
 def cli(argv=None) -> None:
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] != "train":
-        sys.exit("usage: python -m yolox_amd train -c <config> [-d N] [-b B] [--fp16] [-D k=v ...]")
+        sys.exit("usage: python -m yolox_amd train -c <config> [-d N] [-b B] [--fp16] [--resume] [--ckpt FILE] "
+                 "[-e N] [-D k=v ...]")
     main(argv[1:])

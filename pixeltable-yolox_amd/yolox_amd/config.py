@@ -168,6 +168,12 @@ class YoloxConfig:
         sampler = InfiniteSampler(len(ds), seed=seed)
         return MosaicBatches(ds, sampler, batch_size)
 
+    def get_eval_dataset(self, **kwargs):
+        """config.py:350-365's dataset half: the ``pull_item`` detection dataset (with ``.coco`` and
+        ``.class_ids``) the trainer evaluates on every ``eval_interval`` epochs.  None here (no
+        dataset readers); a ``module:Class`` config overrides it (kwargs: ``testdev``, ``legacy``)."""
+        return None
+
     def get_eval_loader(self, batch_size: int, is_distributed: bool, dataset=None, testdev: bool = False,
                         legacy: bool = False):
         """config.py:350-382 over any ``pull_item`` detection dataset with ``.coco`` (the ground
@@ -176,9 +182,12 @@ class YoloxConfig:
         ``legacy``: ValTransform(legacy=True)'s channel flip + /255 + mean/std, data_augment.py:236-240);
         distributed: batch_size // world per rank over the rank's contiguous-strided shard (the
         DistributedSampler without its padding duplicates).  COCO dataset readers are out of scope
-        (no datasets offline): ``dataset`` is required -- ``testdev`` picks the reference's
-        annotation file (test_ann), so here it is the caller's choice of ``dataset``."""
+        (no datasets offline): ``dataset`` is the caller's, or what ``get_eval_dataset`` returns --
+        ``testdev`` picks the reference's annotation file (test_ann), so here it is the choice of
+        that dataset."""
         from .evaluators.coco_evaluator import EvalLoader
+        if dataset is None:
+            dataset = self.get_eval_dataset(testdev=testdev, legacy=legacy)
         if dataset is None:
             raise NotImplementedError("COCO dataset readers are out of scope: pass dataset= (pull_item, coco, "
                                       "class_ids)")

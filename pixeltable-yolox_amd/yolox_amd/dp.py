@@ -145,6 +145,49 @@ class GradReducer:
                 self.flat.mul_(1.0 / self.world)
 
 
+def all_reduce_sum(t: torch.Tensor, group=None) -> None:
+    """One all-reduce (sum) of ``t`` in place, issued the way GradReducer issues a bucket's: through
+    _CudaOps on the current stream for a device tensor, plain ``dist.all_reduce`` for a host one
+    (gloo and RCCL both), then waited for."""
+    if t.is_cuda:
+        ops = _CudaOps()
+        w = ops.all_reduce(t, ops.current(t.device), group)
+    else:
+        w = dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group, async_op=True)
+    w.wait()
+
+
+_ASYNC_NORM = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.InstanceNorm1d, nn.InstanceNorm2d,
+               nn.InstanceNorm3d)
+
+
+def all_reduce_norm(module: nn.Module, group=None) -> None:
+    """utils/allreduce_norm.py:30-101: average the normalisation layers' state over the ranks.
+    ``broadcast_buffers=False`` leaves the BN running statistics rank-local while training; before
+    an evaluation every state_dict entry of every BatchNorm / InstanceNorm submodule (weight, bias,
+    running_mean, running_var, num_batches_tracked; named_modules order) is flattened into one
+    float32 tensor, summed over the ranks in one all-reduce, divided by the world size and copied
+    back in each entry's dtype.  A world of one, or no process group, changes nothing."""
+    if not (dist.is_available() and dist.is_initialized()):
+        return
+    world = dist.get_world_size(group)
+    if world == 1:
+        return
+    states = [v for _, child in module.named_modules() if isinstance(child, _ASYNC_NORM)
+              for v in child.state_dict().values()]
+    if not states:
+        return
+    with torch.no_grad():
+        flat = torch.cat([v.detach().flatten().to(torch.float32) for v in states])
+        all_reduce_sum(flat, group)
+        flat /= world
+        for v, mean in zip(states, torch.split(flat, [v.numel() for v in states])):
+            v.copy_(mean.view_as(v))  # casts to the entry's dtype (num_batches_tracked stays integer)
+    m = module.module if hasattr(module, "module") else module
+    if hasattr(m, "weights_changed"):
+        m.weights_changed()
+
+
 class DistributedDataParallel(nn.Module):
     """Drop-in for ``torch.nn.parallel.DistributedDataParallel`` around a YoloxModule
     (trainer.py:168-169): same constructor arguments, ``.module`` attribute, forward

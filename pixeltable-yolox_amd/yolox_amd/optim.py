@@ -58,8 +58,9 @@ class FusedStep:
                 and optimizer.state[p]["momentum_buffer"] is not None]
         if held and len(held) != len(params):
             raise ValueError("FusedStep: momentum buffers exist for some parameters only")
-        for p in held:  # resume: continue from the optimizer's buffers
+        for p in held:  # resume: continue from the optimizer's buffers, which become the views
             self.bufs[id(p)].copy_(optimizer.state[p]["momentum_buffer"])
+            optimizer.state[p]["momentum_buffer"] = self.bufs[id(p)]
         self.first = not held
         # EMA pairs (ema tensor, model tensor) over floating state_dict entries (ema.py:50-58)
         self.ema_of, self.ema_only = {}, []

@@ -399,14 +399,16 @@ class TrainGraph:
         stream = torch.cuda.current_stream(self.device)
         side = self._wside is not None and stream == self._wside  # each stream tunes into its own sink
         scratch = self._scratch_side if side else self._scratch
-        if scratch.numel() < out_bytes:
-            scratch = torch.empty(out_bytes, dtype=torch.uint8, device=self.device)
+        if scratch.numel() < out_bytes + 16:
+            scratch = torch.empty(out_bytes + 16, dtype=torch.uint8, device=self.device)
             if side:
                 self._scratch_side = scratch
             else:
                 self._scratch = scratch
         real = getattr(d, out_field)
-        setattr(d, out_field, scratch.data_ptr())
+        # at the real destination's 16-byte phase (the head's class rows start 20 bytes into a raw row): a
+        # candidate that needs an aligned destination must be refused here, not win and fail on the real one
+        setattr(d, out_field, scratch.data_ptr() + real % 16)
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         st, ref = self.stream, C.byref(d)
         best = (float("inf"), 0)
@@ -424,7 +426,7 @@ class TrainGraph:
                 if ms < best[0]:
                     best = (ms, tile)
                 if _CHECK_DET:
-                    sink = scratch[:out_bytes]
+                    sink = scratch[:out_bytes + 16]
                     sink.zero_()
                     fn(ref, st)
                     first = sink.clone()
@@ -703,11 +705,19 @@ class TrainGraph:
                 preds.data_ptr(), raw.data_ptr(), labels.data_ptr(), B, A, nc, L, lhw, strides, len(hw),
                 fg.data_ptr(), matched.data_ptr(), piou.data_ptr(), num_fg.data_ptr(), self.grad_total.data_ptr(),
                 int(use_l1), self.dcode, g_ro.data_ptr(), g_cls.data_ptr(), self.stream, iou_type), "loss bwd")
+            epc = 16 // self.esize
+            ncp = (nc + epc - 1) // epc * epc
+            if ncp != nc:
+                # the weight / data gradient kernels read dy in 16-byte chunks: class rows padded with
+                # zeros, as the loss kernel pads the 5 reg | obj rows to 8
+                g_pad = torch.zeros(B, A, ncp, dtype=self.dtype, device=self.device)
+                g_pad[..., :nc].copy_(g_cls)
+                g_cls = g_pad
             gb = self.grads
             for k, r, c, w_ro, a0, h, w in reversed(levels):
                 for g_all, ch, feat, wmat, convs in (
                         (g_ro, 8, r, w_ro, (head.reg_preds[k], head.obj_preds[k])),
-                        (g_cls, nc, c, head.cls_preds[k].weight.detach().reshape(nc, -1), (head.cls_preds[k],))):
+                        (g_cls, ncp, c, head.cls_preds[k].weight.detach().reshape(nc, -1), (head.cls_preds[k],))):
                     cout = sum(cv.out_channels for cv in convs)
                     dys = N.Src()
                     dys.ptr = g_all.data_ptr() + a0 * ch * self.esize

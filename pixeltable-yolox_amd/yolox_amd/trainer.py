@@ -203,10 +203,27 @@ class Trainer:
     ``config.preprocess`` to the current multiscale size, autocast forward, scaled backward,
     fused SGD + EMA (+ GradScaler) step, LR update; ``after_iter`` redraws the input size
     every 10 iterations on rank 0 and broadcasts it (:301-306).  Logging is a print every
-    ``print_interval`` iterations on rank 0; evaluation / checkpoint files are out of scope
-    (DESIGN.md).  ``args.max_iter`` (not in the reference) stops after that many iterations."""
+    ``print_interval`` iterations on rank 0.  ``args.max_iter`` (not in the reference) stops
+    after that many iterations.
+
+    Epoch ends (:232-237, :347-429): ``after_epoch`` writes ``latest_ckpt.pth`` and, every
+    ``eval_interval`` epochs, averages the BN state over the ranks (dp.all_reduce_norm) and
+    evaluates the EMA (the training model with EMA off) in fp32 on ``config.get_eval_dataset()``
+    -- then ``last_epoch_ckpt.pth``, ``best_ckpt.pth`` on a new best AP and, with
+    ``save_history_ckpt``, ``epoch_<n>_ckpt.pth``, all under ``<output_dir>/<name>`` on rank 0;
+    without an evaluation dataset the files are written with ``curr_ap`` None.  ``--resume``
+    continues from such a file (model = the saved EMA weights, optimizer, best AP, epoch and,
+    under --fp16, the GradScaler), ``--ckpt`` alone loads matching weights for fine-tuning
+    (:312-345; DESIGN.md has the file format)."""
+
+    # before_train builds these; until then there is no state and save_ckpt writes nothing
+    rank = 0
+    optimizer = None
+    ema_model = None
 
     def __init__(self, config, args):
+        import os
+
         from .launch import get_local_rank, get_rank, get_world_size
         self.exp = config
         self.args = args
@@ -222,16 +239,28 @@ class Trainer:
         self.input_size = tuple(config.input_size)
         self.start_epoch = 0
         self.last = None  # (progress, input_size, detached loss) of the latest iteration only
+        self.best_ap = 0
+        self.save_history_ckpt = config.save_history_ckpt
+        # created by the first save (rank 0), not here
+        self.file_name = os.path.join(config.output_dir, getattr(args, "name", None) or config.name)
 
     def train(self) -> None:
         self.before_train()
-        self.train_in_epoch()
+        try:
+            self.train_in_epoch()
+        finally:
+            self.after_train()
 
     def train_in_epoch(self) -> None:
         for self.epoch in range(self.start_epoch, self.max_epoch):
             self.before_epoch()
             if not self.train_in_iter():
-                return
+                return  # cut short by --max-iter inside the epoch: no epoch end
+            self.after_epoch()
+
+    def after_train(self) -> None:
+        if self.rank == 0:
+            print(f"Training of experiment is done and the best AP is {self.best_ap * 100:.2f}", flush=True)
 
     def train_in_iter(self) -> bool:
         limit = getattr(self.args, "max_iter", None)
@@ -253,7 +282,8 @@ class Trainer:
         model = self.exp.get_model()
         model.to(self.device)
         self.optimizer = self.exp.get_optimizer(self.args.batch_size)
-        self.no_aug = self.start_epoch >= self.max_epoch - self.exp.no_aug_epochs
+        model = self.resume_train(model)  # sets start_epoch
+        self.no_aug =self.start_epoch >= self.max_epoch - self.exp.no_aug_epochs
         self.train_loader = self.exp.get_data_loader(batch_size=self.args.batch_size,
                                                      is_distributed=self.is_distributed, no_aug=self.no_aug,
                                                      dataset_size=getattr(self.args, "dataset_size", 118287))
@@ -267,13 +297,105 @@ class Trainer:
             self.ema_model = ModelEMA(model, 0.9998)
             self.ema_model.updates = self.max_iter * self.start_epoch
         self.model = model
+        # after the resume: the momentum buffers it loaded become views of the fused step's buffer
         self.fused = FusedStep(model, self.optimizer, self.ema_model)
+        dataset = self.exp.get_eval_dataset(testdev=False, legacy=False)
+        self.evaluator = None if dataset is None else self.exp.get_evaluator(
+            batch_size=self.args.batch_size, is_distributed=self.is_distributed, dataset=dataset)
+
+    def resume_train(self, model):
+        """trainer.py:312-345.  --resume: model, optimizer, best AP and epoch (and, under --fp16, the
+        GradScaler) from ``args.ckpt`` or ``<file_name>/latest_ckpt.pth``; the file's model is the
+        EMA's weights when EMA is on, so training continues from those, and before_train's EMA is
+        a fresh copy of them with ``updates = max_iter * start_epoch``.  --ckpt alone: the
+        checkpoint's matching weights (load_ckpt), everything else fresh."""
+        import os
+
+        from .utils.checkpoint import load_ckpt
+        ckpt_file = getattr(self.args, "ckpt", None)
+        if getattr(self.args, "resume", False):
+            if ckpt_file is None:
+                ckpt_file = os.path.join(self.file_name, "latest_ckpt.pth")
+            ckpt = torch.load(ckpt_file, map_location=self.device, weights_only=True)
+            model.load_state_dict(ckpt["model"])
+            self.optimizer.load_state_dict(ckpt["optimizer"])
+            self.best_ap = ckpt.pop("best_ap", 0)
+            start_epoch = getattr(self.args, "start_epoch", None)
+            self.start_epoch = start_epoch - 1 if start_epoch is not None else ckpt["start_epoch"]
+            if self.amp_training and "scaler" in ckpt:
+                self.scaler.load_state_dict(ckpt["scaler"])
+            if self.rank == 0:
+                print(f"loaded checkpoint '{ckpt_file}' (epoch {self.start_epoch})", flush=True)
+        else:
+            if ckpt_file is not None:
+                if self.rank == 0:
+                    print(f"loading checkpoint '{ckpt_file}' for fine tuning", flush=True)
+                ckpt = torch.load(ckpt_file, map_location=self.device, weights_only=True)["model"]
+                model = load_ckpt(model, ckpt)
+            self.start_epoch = 0
+        return model
 
     def before_epoch(self) -> None:
         if self.epoch + 1 == self.max_epoch - self.exp.no_aug_epochs or self.no_aug:
             self.train_loader.close_mosaic()
             m = self.model.module if self.is_distributed else self.model
             m.head.use_l1 = True
+            self.exp.eval_interval = 1
+            if not self.no_aug:
+                self.save_ckpt("last_mosaic_epoch")
+
+    def after_epoch(self) -> None:
+        """trainer.py:232-237."""
+        from .dp import all_reduce_norm
+        self.save_ckpt("latest")
+        if (self.epoch + 1) % self.exp.eval_interval == 0:
+            all_reduce_norm(self.model)
+            self.evaluate_and_save_model()
+
+    def evaluate_and_save_model(self) -> None:
+        """trainer.py:347-398: fp32 evaluation of the EMA (the unwrapped training model with EMA
+        off) in eval mode for the call only, then last_epoch / best / epoch_<n> checkpoints."""
+        from .launch import synchronize
+        if self.evaluator is None:
+            if self.rank == 0:
+                print(f"no evaluation dataset (config.get_eval_dataset): evaluation of epoch {self.epoch + 1} "
+                      "is skipped", flush=True)
+            ap50_95, update_best = None, False
+        else:
+            evalmodel = self.ema_model.ema if self.use_model_ema else self.model
+            evalmodel = evalmodel.module if hasattr(evalmodel, "module") else evalmodel
+            modes = [(m, m.training) for m in evalmodel.modules()]
+            try:
+                (ap50_95, ap50, summary), _ = self.exp.eval(evalmodel, self.evaluator, self.is_distributed,
+                                                            return_outputs=True)
+            finally:
+                for m, training in modes:
+                    m.training = training
+            update_best = ap50_95 > self.best_ap
+            self.best_ap = max(self.best_ap, ap50_95)
+            if self.rank == 0:
+                print(f"evaluation of epoch {self.epoch + 1}: AP50:95 {ap50_95:.4f}, AP50 {ap50:.4f}, "
+                      f"best AP50:95 {self.best_ap:.4f}\n{summary or ''}", flush=True)
+            synchronize()
+        self.save_ckpt("last_epoch", update_best, ap=ap50_95)
+        if self.save_history_ckpt:
+            self.save_ckpt(f"epoch_{self.epoch + 1}", ap=ap50_95)
+
+    def save_ckpt(self, ckpt_name: str, update_best_ckpt: bool = False, ap=None) -> None:
+        """trainer.py:400-416 on rank 0: ``<file_name>/<ckpt_name>_ckpt.pth`` with the reference's
+        keys (plus ``scaler`` under --fp16, which the reference ignores).  The model is the EMA
+        module, or the unwrapped training model: keys never carry DDP's ``module.`` prefix."""
+        from .utils.checkpoint import save_checkpoint
+        if self.rank != 0 or self.optimizer is None:
+            return
+        save_model = self.ema_model.ema if self.ema_model is not None else self.model
+        save_model = save_model.module if hasattr(save_model, "module") else save_model
+        state = {"start_epoch": self.epoch + 1, "model": save_model.state_dict(),
+                 "optimizer": self.optimizer.state_dict(), "best_ap": self.best_ap, "curr_ap": ap}
+        if self.amp_training:
+            state["scaler"] = self.scaler.state_dict()
+        save_checkpoint(state, update_best_ckpt, self.file_name, ckpt_name)
+        print(f"saved {ckpt_name}_ckpt.pth to {self.file_name}", flush=True)
 
     def train_one_iter(self) -> None:
         inps, targets = self.train_loader.next()
