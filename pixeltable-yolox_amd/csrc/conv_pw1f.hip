@@ -166,14 +166,16 @@ static int launch_pw1f(const ConvParams& p, hipStream_t st) {
 }
 
 int conv_pw1f_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st) {
-    bool ok = dtype == YXH_F32 && p.taps == 1 && p.stride == 1 && p.pad == 0 && p.act < YXH_ACT_DECODE &&
+    // (no residual: the epilogue has no add for one, and the training path's 1x1s take none)
+    bool ok = dtype == YXH_F32 && p.taps == 1 && p.stride == 1 && p.pad == 0 && p.act < YXH_ACT_DECODE && !p.res &&
               p.cin % 4 == 0 && (p.nsrc == 1 || p.src0_ch % 4 == 0) && p.dst_cs % 4 == 0 &&
               (p.dst_dense || p.dst_bs % 4 == 0) && ((uintptr_t)p.dst % 16) == 0 && ((uintptr_t)p.w % 16) == 0;
     for (int s = 0; s < p.nsrc; ++s)
         ok &= (s == 0 || !p.sup[s]) && p.scs[s] % 4 == 0 && p.sbs[s] % 4 == 0 && ((uintptr_t)p.sptr[s] % 16) == 0 &&
               (p.sup[s] ? p.sw[s] * 2 == p.out_w : p.sw[s] == p.out_w);
     if (!ok) {
-        set_error("conv_pw1f: fp32 1x1 s1 conv over 16-byte aligned sources (the first may be x2 upsampled)");
+        set_error("conv_pw1f: fp32 1x1 s1 conv over 16-byte aligned sources (the first may be x2 upsampled), no "
+                  "residual");
         return YXH_EUNSUPPORTED;
     }
     switch (id) {

@@ -350,8 +350,11 @@ static int pwf_dispatch_t(int id, const ConvParams& p, hipStream_t st) {
 int conv_pwf_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st) {
     // an fp32 dst (16-bit operands): the training step's 1x1 data gradient -- no activation / residual,
     // 16-byte rows of whole 4-channel groups (vec_store is the 16-byte test for an fp32 dst)
-    const bool f32ok = !p.dst_f32 || (p.act == YXH_ACT_NONE && !p.res && p.cout % 4 == 0);
-    bool dense = p.taps == 1 && p.stride == 1 && p.pad == 0 && f32ok && p.act < YXH_ACT_DECODE && p.dst_dense &&
+    const bool f32ok = !p.dst_f32 || (p.act == YXH_ACT_NONE && !p.res);
+    // a lane stores (and reads the residual of) whole 4-channel groups: a cout tail inside a group would be
+    // written past the destination's channel slice
+    bool dense = p.taps == 1 && p.stride == 1 && p.pad == 0 && f32ok && p.cout % 4 == 0 && p.act < YXH_ACT_DECODE &&
+                 p.dst_dense &&
                  (!p.res || p.res_dense) && p.vec_store && (!p.res || p.vec_res);
     for (int s = 0; s < p.nsrc; ++s) {
         if (s == 0 && p.sup[0] == 1)  // nearest-x2 upsampled first source: any image stride
@@ -361,7 +364,7 @@ int conv_pwf_dispatch(int dtype, int id, const ConvParams& p, hipStream_t st) {
     }
     if (!dense) {
         set_error("conv_pwf needs a 1x1 s1 conv over dense sources (the first may be x2 upsampled) into a dense "
-                  "16-bit dst (or an fp32 one without activation / residual)");
+                  "16-bit dst (or an fp32 one without activation / residual), cout a multiple of 4");
         return YXH_EUNSUPPORTED;
     }
     const long long img0 = p.sup[0] ? (p.M / p.ohw) * p.sbs[0] : (long long)p.M * p.scs[0];

@@ -75,10 +75,11 @@ def ref_conv(x, conv, bn, act):
 
 
 def run_conv(srcs, conv, bn, dtype, act="silu", residual=None, out=None, out_coff=0, out_c=None, tile=0, flags=0,
-             pre=None, groups2=False, frag=False, post=None, head=None):
+             pre=None, groups2=False, frag=False, post=None, head=None, grid_cap=0, packed=None):
     """srcs: list of (nhwc tensor [B,h,w,C], coff, ch, upsample).  post: (packed weight, bias,
     (post_src tensor, coff, ch) or None, post_dst tensor, coff, post_cout): a 1x1 post conv
-    whose output goes to post_dst instead of the conv's own output."""
+    whose output goes to post_dst instead of the conv's own output.  grid_cap: yxh_conv_desc.grid_cap.
+    packed: the (weight, bias) pack() made for this conv, to read back what the kernel read."""
     n = N()
     B = srcs[0][0].shape[0]
     ups = srcs[0][3]
@@ -86,7 +87,7 @@ def run_conv(srcs, conv, bn, dtype, act="silu", residual=None, out=None, out_cof
     k, s, pd = conv.kernel_size[0], conv.stride[0], conv.padding[0]
     oh, ow = (in_h + 2 * pd - k) // s + 1, (in_w + 2 * pd - k) // s + 1
     cin = sum(c for _, _, c, _ in srcs)
-    w, b = pack(conv, bn, dtype, (cin // 2 if groups2 else cin) if conv.groups == 1 else None)
+    w, b = packed or pack(conv, bn, dtype, (cin // 2 if groups2 else cin) if conv.groups == 1 else None)
     cout = conv.out_channels
     if out is None:
         out = torch.zeros(B, oh, ow, out_c or cout, dtype=dtype, device=DEV)
@@ -115,6 +116,7 @@ def run_conv(srcs, conv, bn, dtype, act="silu", residual=None, out=None, out_cof
     d.act = n.ACT_CODE[act]
     d.tile = tile
     d.flags = flags
+    d.grid_cap = grid_cap
     if pre is not None:  # fused Bottleneck conv1 (packed weight, bias)
         d.pre_weight, d.pre_bias = pre[0].data_ptr(), pre[1].data_ptr()
     if groups2:  # output half g reads source channels [g*cin, (g+1)*cin)
