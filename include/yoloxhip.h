@@ -352,6 +352,34 @@ int yxh_augment_batch(const uint8_t* pool, const yxh_aug_image* images, int32_t 
 size_t yxh_sizeof_aug_image(void);
 
 /*
+ * yxh_resize_u8_batch: CocoDataset.load_resized_img (datasets/coco.py:131-139: cv2.resize(img,
+ * (int(w*r), int(h*r)), INTER_LINEAR)) for a ragged batch of decoded images in one launch -- how
+ * images enter the pool yxh_augment_batch reads.  `src`: device bytes holding the decoded images;
+ * `images` (device, one per image): where each lies, its size, the resized size the host computed
+ * and where in `dst` the packed dst_h x dst_w x 3 result goes.  The arithmetic is
+ * yxh_letterbox_batch's without the canvas: scale = 1.0 / ((double)dst / src) per axis; equal
+ * sizes copy; both scales within 2.22e-16 of 2 take cv2's INTER_AREA path ((a+b+c+d+2)>>2);
+ * otherwise the 11-bit fixed-point bilinear with border clamp.  YXH_RESIZE_SWAP_RB exchanges
+ * channels 0 and 2 on the way out (PIL decodes RGB, the pool holds cv2.imread's BGR).  No byte
+ * outside [dst_offset, dst_offset + dst_h*dst_w*3) is written; a descriptor with an empty size, a
+ * negative offset or a dst_offset that is no multiple of 16 is skipped.  The caller checks that
+ * both ranges lie inside its buffers.  `dst` is 16-byte aligned.
+ *
+ * Added without a new YXH_ABI_VERSION: the entry is additive (nothing existing changes layout or
+ * meaning), and yxh_sizeof_resize_image is the descriptor's own layout self-check for bindings.
+ */
+typedef struct {
+    int64_t src_offset;   /* bytes into src: uint8 HWC, packed rows of src_w * 3, any alignment */
+    int64_t dst_offset;   /* bytes into dst, a multiple of 16 */
+    int32_t src_h, src_w;
+    int32_t dst_h, dst_w; /* the host's int(src_h * r), int(src_w * r) */
+} yxh_resize_image;
+enum yxh_resize_flags { YXH_RESIZE_SWAP_RB = 1 };
+int yxh_resize_u8_batch(const uint8_t* src, const yxh_resize_image* images, int32_t batch,
+                        int32_t flags, uint8_t* dst, void* stream);
+size_t yxh_sizeof_resize_image(void);
+
+/*
  * yxh_postprocess: utils.postprocess (utils/boxes.py:31-75) with torchvision
  * nms / batched_nms semantics (CPU branch rule: boxes.numel() > vanilla_numel ->
  * per-class NMS, else coordinate-offset NMS) on device.

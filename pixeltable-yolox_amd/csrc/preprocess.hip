@@ -43,13 +43,8 @@ __device__ __forceinline__ void coeff(int d, double scale, int ssize, int& s0, i
     a1 = (int)rintf(f * 2048.0f);
 }
 
-__device__ void lb_params(const yxh_lb_image& im, int th, int tw, LbParams& p) {
-    p.sh = im.src_h;
-    p.sw = im.src_w;
-    p.off = im.src_offset;
-    const double r = fmin((double)th / p.sh, (double)tw / p.sw);
-    p.rw = (int)(p.sw * r);
-    p.rh = (int)(p.sh * r);
+// cv2's scale factors and the path they select, from the source and resized sizes
+__device__ __forceinline__ void lb_mode(LbParams& p) {
     p.sx = 1.0 / ((double)p.rw / p.sw);
     p.sy = 1.0 / ((double)p.rh / p.sh);
     if (p.rw == p.sw && p.rh == p.sh)
@@ -58,6 +53,26 @@ __device__ void lb_params(const yxh_lb_image& im, int th, int tw, LbParams& p) {
         p.mode = 2;
     else
         p.mode = 1;
+}
+
+__device__ void lb_params(const yxh_lb_image& im, int th, int tw, LbParams& p) {
+    p.sh = im.src_h;
+    p.sw = im.src_w;
+    p.off = im.src_offset;
+    const double r = fmin((double)th / p.sh, (double)tw / p.sw);
+    p.rw = (int)(p.sw * r);
+    p.rh = (int)(p.sh * r);
+    lb_mode(p);
+}
+
+// yxh_resize_u8_batch: the resized size is the host's (CocoDataset's resized_info), the rest as above
+__device__ void rs_params(const yxh_resize_image& im, LbParams& p) {
+    p.sh = im.src_h;
+    p.sw = im.src_w;
+    p.off = im.src_offset;
+    p.rh = im.dst_h;
+    p.rw = im.dst_w;
+    lb_mode(p);
 }
 
 __device__ __forceinline__ void pixel(const uint8_t* src, const LbParams& p, int y, int x, int v[3]) {
@@ -165,6 +180,99 @@ int letterbox_batch_launch(const uint8_t* pool, const yxh_lb_image* images, int 
     hipLaunchKernelGGL(letterbox_batch, dim3((quads + 255) / 256, B), dim3(256), 0, st, pool, images, th, tw, fmt,
                        dst);
     YXH_CHECK_LAUNCH("letterbox_batch");
+    return YXH_OK;
+}
+
+// ---------------------------------------------------------------- dataset resize into the pool
+// CocoDataset.load_resized_img (datasets/coco.py:131-139) for a ragged batch in ONE launch: the
+// letterbox arithmetic above without the canvas, each image written packed (rows of dst_w * 3
+// bytes) at its own 16-aligned offset -- the layout yxh_augment_batch reads its pool in.  An
+// image is a flat run of dst_h * dst_w pixels, 4 consecutive pixels (12 bytes, dword-aligned
+// whatever dst_w is) per lane; blockIdx.y is the image, the blocks of a row of the grid stride
+// over its groups, so one grid serves every size in the batch.  The last, partial group is
+// stored by bytes: nothing outside [dst_offset, dst_offset + dst_h*dst_w*3) is written.  A
+// descriptor with an empty size or a misaligned / negative offset is skipped whole.
+constexpr int kResizeBlocksPerImage = 128;
+
+__global__ __launch_bounds__(256) void resize_u8_batch(const uint8_t* pool, const yxh_resize_image* images,
+                                                       int swap_rb, uint8_t* dst) {
+    __shared__ LbParams sp;
+    __shared__ long long sdst;
+    const int b = blockIdx.y;
+    if (threadIdx.x == 0) {
+        const yxh_resize_image im = images[b];
+        rs_params(im, sp);
+        const bool ok = im.src_h > 0 && im.src_w > 0 && im.dst_h > 0 && im.dst_w > 0 && im.src_offset >= 0 &&
+                        im.dst_offset >= 0 && (im.dst_offset & 15) == 0;
+        sdst = ok ? im.dst_offset : -1;
+    }
+    __syncthreads();
+    const LbParams p = sp;
+    if (sdst < 0) return;
+    const uint8_t* src = pool + p.off;
+    uint8_t* out = dst + sdst;
+    const long long npix = (long long)p.rh * p.rw;
+    const long long groups = (npix + 3) >> 2;
+    for (long long g = (long long)blockIdx.x * 256 + threadIdx.x; g < groups; g += (long long)gridDim.x * 256) {
+        const long long p0 = g * 4;
+        const int n = (int)min(4LL, npix - p0);  // pixels of this group
+        uint8_t t[12];
+        if (p.mode == 0 && n == 4) {  // copy: source and destination are the same flat run
+            const uint8_t* s = src + p0 * 3;
+            if (((uintptr_t)s & 3) == 0) {
+                uint32_t w[3];
+                w[0] = ((const uint32_t*)s)[0];
+                w[1] = ((const uint32_t*)s)[1];
+                w[2] = ((const uint32_t*)s)[2];
+                __builtin_memcpy(t, w, 12);
+            } else {
+#pragma unroll
+                for (int i = 0; i < 12; ++i) t[i] = s[i];
+            }
+        } else {
+            int y = (int)(p0 / p.rw), x = (int)(p0 - (long long)y * p.rw);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                int v[3] = {0, 0, 0};
+                if (k < n) pixel(src, p, y, x, v);
+                t[3 * k] = (uint8_t)v[0];
+                t[3 * k + 1] = (uint8_t)v[1];
+                t[3 * k + 2] = (uint8_t)v[2];
+                if (++x == p.rw) { x = 0; ++y; }
+            }
+        }
+        if (swap_rb) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint8_t c0 = t[3 * k];
+                t[3 * k] = t[3 * k + 2];
+                t[3 * k + 2] = c0;
+            }
+        }
+        uint8_t* d = out + p0 * 3;
+        if (n == 4) {
+            uint32_t w[3];
+            __builtin_memcpy(w, t, 12);
+            ((uint32_t*)d)[0] = w[0];
+            ((uint32_t*)d)[1] = w[1];
+            ((uint32_t*)d)[2] = w[2];
+        } else {
+#pragma unroll
+            for (int i = 0; i < 9; ++i)
+                if (i < 3 * n) d[i] = t[i];
+        }
+    }
+}
+
+int resize_u8_batch_launch(const uint8_t* src, const yxh_resize_image* images, int B, int flags, uint8_t* dst,
+                           hipStream_t st) {
+    YXH_CHECK_ARG(src && images && dst, "resize_u8: null pointer");
+    YXH_CHECK_ARG(B > 0 && B <= 65535, "resize_u8 batch %d", B);
+    YXH_CHECK_ARG((flags & ~YXH_RESIZE_SWAP_RB) == 0, "resize_u8: unknown flags 0x%x", flags);
+    YXH_CHECK_ARG(((uintptr_t)dst & 15) == 0, "resize_u8 dst must be 16-byte aligned");
+    hipLaunchKernelGGL(resize_u8_batch, dim3(kResizeBlocksPerImage, B), dim3(256), 0, st, src, images,
+                       flags & YXH_RESIZE_SWAP_RB, dst);
+    YXH_CHECK_LAUNCH("resize_u8_batch");
     return YXH_OK;
 }
 

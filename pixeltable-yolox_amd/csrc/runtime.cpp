@@ -68,6 +68,8 @@ int iou_loss_bwd_launch(const float* pred, const float* target, long long n, int
                         const float* grad_out, float* g_pred, float* g_target, hipStream_t st);
 int letterbox_batch_launch(const uint8_t* pool, const yxh_lb_image* images, int B, int th, int tw, int fmt,
                            void* dst, hipStream_t st);
+int resize_u8_batch_launch(const uint8_t* src, const yxh_resize_image* images, int B, int flags, uint8_t* dst,
+                           hipStream_t st);
 size_t reduce_workspace(int C);
 int bn_stats(int dt, int B, const yxh_src* y, const float* gamma, const float* beta, float* rmean, float* rvar,
              float eps, float momentum, float* stats, void* ws, size_t ws_bytes, hipStream_t st);
@@ -198,6 +200,13 @@ int yxh_augment_batch(const uint8_t* pool, const yxh_aug_image* images, int32_t 
 }
 
 size_t yxh_sizeof_aug_image(void) { return sizeof(yxh_aug_image); }
+
+int yxh_resize_u8_batch(const uint8_t* src, const yxh_resize_image* images, int32_t batch, int32_t flags,
+                        uint8_t* dst, void* stream) {
+    return resize_u8_batch_launch(src, images, batch, flags, dst, (hipStream_t)stream);
+}
+
+size_t yxh_sizeof_resize_image(void) { return sizeof(yxh_resize_image); }
 
 size_t yxh_postprocess_workspace_bytes(int32_t batch, int32_t anchors) { return pp_workspace(batch, anchors); }
 

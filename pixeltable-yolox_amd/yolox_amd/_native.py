@@ -26,6 +26,7 @@ ACT_NONE, ACT_SILU, ACT_RELU, ACT_LRELU, ACT_DECODE, ACT_DECODE_TRAIN, ACT_DECOD
 NCHW, NHWC = 0, 1
 OP_CONV, OP_FOCUS, OP_SPP, OP_STEM, OP_HEAD, OP_STEM2 = 0, 1, 2, 3, 4, 5
 LB_F32_NCHW, LB_U8_NHWC, LB_BF16_NHWC = 0, 1, 2
+RESIZE_SWAP_RB = 1
 IOU_LOSS_IOU, IOU_LOSS_GIOU = 0, 1
 REDUCE_NONE, REDUCE_SUM, REDUCE_MEAN = 0, 1, 2
 IOU_LOSS_CODE = {"iou": IOU_LOSS_IOU, "giou": IOU_LOSS_GIOU}
@@ -141,6 +142,12 @@ class AugImage(C.Structure):
                 ("x_off", C.c_int32), ("y_off", C.c_int32)]
 
 
+class ResizeImage(C.Structure):
+    """yxh_resize_image (include/yoloxhip.h): one image of a yxh_resize_u8_batch launch."""
+    _fields_ = [("src_offset", C.c_int64), ("dst_offset", C.c_int64), ("src_h", C.c_int32), ("src_w", C.c_int32),
+                ("dst_h", C.c_int32), ("dst_w", C.c_int32)]
+
+
 class HeadDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("batch", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cin", C.c_int32),
                 ("num_classes", C.c_int32), ("reg", Src), ("cls", Src), ("w_reg", C.c_void_p), ("b_reg", C.c_void_p),
@@ -210,6 +217,8 @@ def lib():
             "yxh_letterbox_batch": ([vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
             "yxh_augment_batch": ([vp, vp, i32, i32, i32, vp, vp, vp], C.c_int),
             "yxh_sizeof_aug_image": ([], sz),
+            "yxh_resize_u8_batch": ([vp, vp, i32, i32, vp, vp], C.c_int),
+            "yxh_sizeof_resize_image": ([], sz),
             "yxh_postprocess_workspace_bytes": ([i32, i32], sz),
             "yxh_set_nms_mask_budget": ([sz], None),
             "yxh_postprocess": ([vp, i32, i32, i32, f32, f64, i32, i64, vp, vp, vp, sz, vp], C.c_int),
@@ -270,7 +279,8 @@ def lib():
         if L.yxh_abi_version() != ABI_VERSION:
             raise NativeError(f"ABI mismatch: library {L.yxh_abi_version()} vs binding {ABI_VERSION}")
         if (L.yxh_sizeof_op() != C.sizeof(Op) or L.yxh_sizeof_conv_desc() != C.sizeof(ConvDesc)
-                or L.yxh_sizeof_aug_image() != C.sizeof(AugImage)):
+                or L.yxh_sizeof_aug_image() != C.sizeof(AugImage)
+                or L.yxh_sizeof_resize_image() != C.sizeof(ResizeImage)):
             raise NativeError("struct layout mismatch between yoloxhip.h and _native.py")
         _lib = L
     return _lib
@@ -284,7 +294,8 @@ EXPORTED = ["yxh_abi_version", "yxh_last_error", "yxh_sizeof_op", "yxh_sizeof_co
             "yxh_upsample_bwd", "yxh_dw_wgrad_workspace_bytes", "yxh_dw_wgrad", "yxh_dw_dgrad", "yxh_resize_bilinear",
             "yxh_head_decode_train", "yxh_yolox_loss_bwd", "yxh_opt_chunk_elems",
             "yxh_yolox_loss_ex", "yxh_yolox_loss_bwd_ex", "yxh_iou_loss_workspace_bytes", "yxh_iou_loss", "yxh_iou_loss_bwd",
-            "yxh_sgd_ema_step", "yxh_amp_found_inf", "yxh_amp_update_scale", "yxh_coco_eval", "yxh_coco_iou"]
+            "yxh_sgd_ema_step", "yxh_amp_found_inf", "yxh_amp_update_scale", "yxh_coco_eval", "yxh_coco_iou",
+            "yxh_resize_u8_batch", "yxh_sizeof_resize_image"]
 
 
 def check(rc: int, what: str = "") -> None:

@@ -9,10 +9,13 @@ GLOBAL batch (each rank trains on b / d images), ``--fp16`` mixed precision thro
 autocast + GradScaler, ``-D`` config overrides, ``--resume`` continue from ``--ckpt`` or
 ``<output_dir>/<name>/latest_ckpt.pth`` (``-e`` overrides the epoch to start at, 1-based),
 ``--ckpt`` alone fine-tune from a checkpoint's matching weights.  Every epoch end writes
-checkpoints there and, with an evaluation dataset (``YoloxConfig.get_eval_dataset`` of a
-``module:Class`` config), evaluates (yolox_amd.trainer).  Added: ``--max-iter`` (stop after
-that many iterations) and ``--dataset-size`` (length of the synthetic COCO-shaped dataset
-that stands in for COCO offline).  Loggers and ``--cache`` are out of scope.
+checkpoints there and, with an evaluation dataset (``YoloxConfig.get_eval_dataset``),
+evaluates (yolox_amd.trainer).  ``-D data_dir=/path/to/COCO`` trains on a COCO-layout directory
+(``annotations/<train_ann>``, ``train2017/``; yolox_amd.data.CocoDataset streamed through an HBM
+pool of ``YOLOX_AMD_DATA_CACHE_GB`` gigabytes, 64 by default) and evaluates on its ``val2017``;
+without ``data_dir`` the training data is synthetic and nothing is evaluated.  Added:
+``--max-iter`` (stop after that many iterations) and ``--dataset-size`` (length of the synthetic
+COCO-shaped dataset).  Loggers and ``--cache`` are out of scope (the HBM pool is the cache).
 """
 from __future__ import annotations
 

@@ -7,9 +7,12 @@ configs are module-level singletons, as in the reference (quirk: they cache the
 model they build, config.py:168-172, 466-469).  The training-side factories the
 trainer calls are here too: ``get_optimizer`` (:307-333), ``get_lr_scheduler``
 (:335-348), ``random_resize`` (:275-294, rank-0 draw broadcast to every rank),
-``preprocess`` (:296-305, bilinear multiscale on the device) and ``get_data_loader`` -- the latter
-over a synthetic COCO-shaped dataset (no datasets offline; COCO files and the
-Mosaic/MixUp CPU pipeline are out of scope).
+``preprocess`` (:296-305, bilinear multiscale on the device), ``get_dataset`` (:179-201),
+``get_data_loader`` and ``get_eval_dataset`` (:350-361).  With ``data_dir`` set they read a
+COCO-layout directory (yolox_amd.data.CocoDataset, streamed into a bounded HBM pool for
+training); with ``data_dir=None`` training data is the synthetic COCO-shaped dataset and there
+is no evaluation dataset.  The reference's fallback to ``$YOLOX_DATADIR/COCO`` when ``data_dir``
+is None is deliberately not copied: None keeps meaning "no files" (DESIGN.md §2).
 """
 from __future__ import annotations
 
@@ -138,15 +141,33 @@ class YoloxConfig:
                            warmup_lr_start=self.warmup_lr, no_aug_epochs=self.no_aug_epochs,
                            min_lr_ratio=self.min_lr_ratio)
 
+    def _check_categories(self, dataset):
+        if len(dataset.class_ids) > self.num_classes:
+            raise ValueError(f"{dataset.json_file} has {len(dataset.class_ids)} categories, the model "
+                             f"{self.num_classes} classes (set num_classes)")
+        return dataset
+
+    def get_dataset(self, cache: bool = False, cache_type: str = "ram"):
+        """config.py:179-201: the training CocoDataset over ``data_dir`` (train_ann, train2017,
+        input_size).  ``cache`` is refused: the images' cache is the loader's HBM pool
+        (StreamedImages, sized by YOLOX_AMD_DATA_CACHE_GB)."""
+        from .data.coco import CocoDataset
+        if cache:
+            raise NotImplementedError("cache: dataset caches are out of scope (the HBM pool is the cache)")
+        if self.data_dir is None:
+            raise ValueError("get_dataset needs data_dir (there is no YOLOX_DATADIR fallback)")
+        return CocoDataset(self.data_dir, self.train_ann, "train2017", self.input_size)
+
     def get_data_loader(self, batch_size: int, is_distributed: bool, no_aug: bool = False, cache_img=None,
                         dataset_size: int = 118287, device=None, distinct_images: int = 512, dataset=None):
         """config.py:203-273 on the device pipeline: MosaicDetection (mosaic / random affine /
         mixup) + TrainTransform (HSV / mirror / padded labels) over a ``pull_item`` detection
         dataset whose images live in HBM (yolox_amd.data.GpuMosaicDetection: the host draws the
         reference's random numbers in its order and does the label arithmetic, one
-        yxh_augment_batch launch renders the batch).  ``dataset`` defaults to the synthetic
-        COCO-shaped one (no datasets offline: ``dataset_size`` items over ``distinct_images``
-        resident images).  The per-rank batch is batch_size // world (:249-250) and every rank
+        yxh_augment_batch launch renders the batch).  ``dataset`` defaults, with ``data_dir`` set,
+        to ``get_dataset()`` streamed through a bounded HBM pool (StreamedImages: decoded on first
+        use by ``data_num_workers`` threads, resized on the device), and otherwise to the synthetic
+        COCO-shaped one (``dataset_size`` items over ``distinct_images`` resident images).  The per-rank batch is batch_size // world (:249-250) and every rank
         reads its rank-strided slice of one seeded shuffled index stream (InfiniteSampler,
         samplers.py:28-82); ``no_aug`` starts with mosaic off (YoloBatchSampler(mosaic=not
         no_aug), :255-260), ``close_mosaic()`` turns it off later (trainer.py:217-230)."""
@@ -156,7 +177,12 @@ class YoloxConfig:
         if is_distributed:
             batch_size = batch_size // get_world_size()
         seed = self.seed if self.seed else 0
-        if dataset is None:
+        resident = None
+        if dataset is None and self.data_dir is not None:
+            from .data.streamed import StreamedImages
+            dataset = self._check_categories(self.get_dataset())
+            resident = StreamedImages(dataset, device or "cuda", workers=self.data_num_workers)
+        elif dataset is None:
             dataset = SyntheticDetectionDataset(dataset_size, self.input_size, seed=seed,
                                                 num_classes=self.num_classes, distinct=distinct_images)
         ds = GpuMosaicDetection(
@@ -164,15 +190,22 @@ class YoloxConfig:
             preproc=TrainTransform(max_labels=120, flip_prob=self.flip_prob, hsv_prob=self.hsv_prob),
             degrees=self.degrees, translate=self.translate, mosaic_scale=self.mosaic_scale,
             mixup_scale=self.mixup_scale, shear=self.shear, enable_mixup=self.enable_mixup,
-            mosaic_prob=self.mosaic_prob, mixup_prob=self.mixup_prob, device=device or "cuda")
+            mosaic_prob=self.mosaic_prob, mixup_prob=self.mixup_prob, device=device or "cuda", resident=resident)
         sampler = InfiniteSampler(len(ds), seed=seed)
         return MosaicBatches(ds, sampler, batch_size)
 
     def get_eval_dataset(self, **kwargs):
         """config.py:350-365's dataset half: the ``pull_item`` detection dataset (with ``.coco`` and
-        ``.class_ids``) the trainer evaluates on every ``eval_interval`` epochs.  None here (no
-        dataset readers); a ``module:Class`` config overrides it (kwargs: ``testdev``, ``legacy``)."""
-        return None
+        ``.class_ids``) the trainer evaluates on every ``eval_interval`` epochs: the CocoDataset over
+        ``data_dir`` (val_ann / val2017, or test_ann / test2017 with ``testdev``; test_size), or None
+        when ``data_dir`` is None.  ``legacy`` is the loader's business here (EvalLoader normalises)."""
+        if self.data_dir is None:
+            return None
+        from .data.coco import CocoDataset
+        testdev = kwargs.get("testdev", False)
+        return self._check_categories(CocoDataset(
+            self.data_dir, self.val_ann if not testdev else self.test_ann,
+            "val2017" if not testdev else "test2017", self.test_size))
 
     def get_eval_loader(self, batch_size: int, is_distributed: bool, dataset=None, testdev: bool = False,
                         legacy: bool = False):
@@ -181,16 +214,15 @@ class YoloxConfig:
         ids) batches letterboxed to test_size on the device (ValTransform = yxh_letterbox_batch;
         ``legacy``: ValTransform(legacy=True)'s channel flip + /255 + mean/std, data_augment.py:236-240);
         distributed: batch_size // world per rank over the rank's contiguous-strided shard (the
-        DistributedSampler without its padding duplicates).  COCO dataset readers are out of scope
-        (no datasets offline): ``dataset`` is the caller's, or what ``get_eval_dataset`` returns --
-        ``testdev`` picks the reference's annotation file (test_ann), so here it is the choice of
-        that dataset."""
+        DistributedSampler without its padding duplicates).  ``dataset`` is the caller's, or what
+        ``get_eval_dataset`` returns (``testdev`` picks test_ann / test2017); without either
+        (``data_dir`` None) there is nothing to evaluate on and this raises."""
         from .evaluators.coco_evaluator import EvalLoader
         if dataset is None:
             dataset = self.get_eval_dataset(testdev=testdev, legacy=legacy)
         if dataset is None:
-            raise NotImplementedError("COCO dataset readers are out of scope: pass dataset= (pull_item, coco, "
-                                      "class_ids)")
+            raise NotImplementedError("no evaluation dataset: set data_dir (a COCO-layout directory) or pass "
+                                      "dataset= (pull_item, coco, class_ids)")
         rank, world = 0, 1
         if is_distributed:
             import torch.distributed as dist

@@ -6,7 +6,9 @@ resized and pasted into a 2H x 2W mosaic canvas, warped by a random affine, mixe
 jittered copy-paste image, HSV-jittered, mirrored and transposed to float32 CHW.  Here:
 
 * the dataset's pull_item images stay RESIDENT in HBM (``ResidentImages``: one byte pool,
-  uploaded once -- the analogue of the reference's ``cache=True``, sized for 288 GB);
+  uploaded once -- the analogue of the reference's ``cache=True``, sized for 288 GB), or, for
+  a dataset on disk, in ``StreamedImages``' bounded pool (streamed.py), filled by ``render``
+  through ``ensure`` with the images the drawn batch reads;
 * the host draws each sample's random parameters with Python ``random`` / ``np.random`` in
   exactly the reference's call order (so a seeded run draws the same augmentation as the
   reference) and computes the labels in numpy with the reference's arithmetic;
@@ -426,6 +428,9 @@ class GpuMosaicDetection:
         input_h, input_w = self._input_dim
         N.require_device(self.images.pool, "resident image pool")
         B = len(params)
+        ensure = getattr(self.images, "ensure", None)
+        if ensure is not None:  # an on-demand pool (StreamedImages): load what this batch reads
+            ensure([i for p in params for i in (p.indices + [p.cp_index] if p.mix else p.indices)])
         descs = (N.AugImage * B)(*[self.pack(p) for p in params])
         host = torch.frombuffer(bytearray(bytes(descs)), dtype=torch.uint8)
         dev_desc = host.to(self.device, non_blocking=False)

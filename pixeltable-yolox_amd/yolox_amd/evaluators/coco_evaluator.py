@@ -124,7 +124,8 @@ class EvalLoader:
                 imgs = legacy_normalize(imgs)
             targets = [it[1] for it in items]
             info = ([int(it[2][0]) for it in items], [int(it[2][1]) for it in items])
-            yield imgs, targets, info, [int(it[3]) for it in items]
+            # an id is an int or CocoDataset's np.array([id])
+            yield imgs, targets, info, [int(np.asarray(it[3]).reshape(-1)[0]) for it in items]
 
 
 class CocoEvaluator:
