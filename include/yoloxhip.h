@@ -274,6 +274,29 @@ int yxh_stem_pack(const float* conv_w, const float* bn_gamma, const float* bn_be
                   void* stream);
 
 /*
+ * The RGB stem of Darknet-53 (darknet.py:31: BaseConv(3, 32, ksize=3, stride=1, act="lrelu") straight
+ * from the image; no Focus).  Added without a new YXH_ABI_VERSION, as yxh_resize_u8_batch was: the
+ * entries are additive, yxh_rgb_stem_conv reuses yxh_stem_desc and sizeof(yxh_op) is unchanged.
+ *
+ * yxh_rgb_stem_pack: BN folded as yxh_stem_pack does; weight [cout][3][3][3] -> [round16(cout)][32] of
+ *   `dtype` with k = (ky*3 + kx)*3 + c (entries 27..31 and the rows past cout zero), bias fp32
+ *   [round16(cout)].  cout <= 64.
+ * yxh_rgb_stem_conv: 3x3 stride-1 pad-1 conv of a 3-channel image (NCHW float32, or NHWC
+ *   uint8 / bf16 / f16 / f32) + folded bias + d->act (none / silu / relu / lrelu) into NHWC rows of
+ *   dst_cstride elements of `dtype` (f32 / bf16 / f16); only channels [0, cout) of a row are written.
+ *   Any h, w >= 1; cout a multiple of 16 up to 64; dst 16-byte aligned rows.  Bad arguments return
+ *   YXH_EINVAL, a valid shape the kernel is not built for YXH_EUNSUPPORTED, both before any launch.
+ * yxh_rgb_pack: the image as NHWC `dst_dtype` with 16 channels (3 used, 13 zero): yxh_focus_pack
+ *   without the space-to-depth, for the generic conv with weights packed at cin_pad 16.
+ */
+int yxh_rgb_stem_pack(const float* conv_w, const float* bn_gamma, const float* bn_beta, const float* bn_mean,
+                      const float* bn_var, float eps, int32_t cout, int32_t dtype, void* w_out, float* b_out,
+                      void* stream);
+int yxh_rgb_stem_conv(const yxh_stem_desc* d, void* stream);
+int yxh_rgb_pack(const void* img, int32_t layout, int32_t img_dtype, int32_t batch, int32_t h, int32_t w,
+                 void* dst, int32_t dst_dtype, void* stream);
+
+/*
  * yxh_spp_maxpool: SPPBottleneck pools (network_blocks.py:129-141): reads channels
  * [0, c) of an NHWC buffer and writes max_pool(k, stride 1, pad k/2) for k = 5, 9,
  * 13 into channels [c, 2c), [2c, 3c), [3c, 4c) of the same buffer.
@@ -703,7 +726,9 @@ int yxh_yolox_loss_bwd_ex(const float* preds, const float* raw, const float* lab
  * reference's eager per-module dispatch).
  */
 enum yxh_op_kind { YXH_OP_CONV = 0, YXH_OP_FOCUS = 1, YXH_OP_SPP = 2, YXH_OP_STEM = 3, YXH_OP_HEAD = 4,
-                   YXH_OP_STEM2 = 5 };
+                   YXH_OP_STEM2 = 5,
+                   YXH_OP_STEM_RGB = 6, /* yxh_rgb_stem_conv over u.stem */
+                   YXH_OP_RGB_PACK = 7  /* yxh_rgb_pack over u.focus */ };
 typedef struct {
     const void* img;
     int32_t layout, img_dtype, batch, h, w, dst_dtype;

@@ -24,7 +24,7 @@ OK, EINVAL, EHIP, EUNSUPPORTED = 0, -1, -2, -3
 F32, BF16, F16, U8 = 0, 1, 2, 3
 ACT_NONE, ACT_SILU, ACT_RELU, ACT_LRELU, ACT_DECODE, ACT_DECODE_TRAIN, ACT_DECODE_RAW = range(7)
 NCHW, NHWC = 0, 1
-OP_CONV, OP_FOCUS, OP_SPP, OP_STEM, OP_HEAD, OP_STEM2 = 0, 1, 2, 3, 4, 5
+OP_CONV, OP_FOCUS, OP_SPP, OP_STEM, OP_HEAD, OP_STEM2, OP_STEM_RGB, OP_RGB_PACK = 0, 1, 2, 3, 4, 5, 6, 7
 LB_F32_NCHW, LB_U8_NHWC, LB_BF16_NHWC = 0, 1, 2
 RESIZE_SWAP_RB = 1
 IOU_LOSS_IOU, IOU_LOSS_GIOU = 0, 1
@@ -212,6 +212,9 @@ def lib():
             "yxh_stem_conv": ([C.POINTER(StemDesc), vp], C.c_int),
             "yxh_stem_s2": ([C.POINTER(Stem2Desc), vp], C.c_int),
             "yxh_stem_pack": ([vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp], C.c_int),
+            "yxh_rgb_stem_pack": ([vp, vp, vp, vp, vp, f32, i32, i32, vp, vp, vp], C.c_int),
+            "yxh_rgb_stem_conv": ([C.POINTER(StemDesc), vp], C.c_int),
+            "yxh_rgb_pack": ([vp, i32, i32, i32, i32, i32, vp, i32, vp], C.c_int),
             "yxh_fold_bn_pack": ([vp, vp, vp, vp, vp, vp, f32, i32, i32, i32, i32, i32, i32, vp, vp, vp],
                                  C.c_int),
             "yxh_letterbox_batch": ([vp, vp, i32, i32, i32, i32, vp, vp], C.c_int),
@@ -295,7 +298,8 @@ EXPORTED = ["yxh_abi_version", "yxh_last_error", "yxh_sizeof_op", "yxh_sizeof_co
             "yxh_head_decode_train", "yxh_yolox_loss_bwd", "yxh_opt_chunk_elems",
             "yxh_yolox_loss_ex", "yxh_yolox_loss_bwd_ex", "yxh_iou_loss_workspace_bytes", "yxh_iou_loss", "yxh_iou_loss_bwd",
             "yxh_sgd_ema_step", "yxh_amp_found_inf", "yxh_amp_update_scale", "yxh_coco_eval", "yxh_coco_iou",
-            "yxh_resize_u8_batch", "yxh_sizeof_resize_image"]
+            "yxh_resize_u8_batch", "yxh_sizeof_resize_image",
+            "yxh_rgb_stem_pack", "yxh_rgb_stem_conv", "yxh_rgb_pack"]
 
 
 def check(rc: int, what: str = "") -> None:

@@ -304,7 +304,29 @@ _PRESETS: dict[str, dict[str, Any]] = {
                        mosaic_scale=(0.5, 1.5), test_size=(416, 416), mosaic_prob=0.5, enable_mixup=False),
 }
 
-_NAMED_CONFIG: dict[str, YoloxConfig] = {n: YoloxConfig(n, **kw) for n, kw in _PRESETS.items()}
+@dataclass
+class YoloxDarknet(YoloxConfig):
+    """YOLOX-Darknet53 (the reference's ``yolox.models`` exports YoloFpn / Darknet / ResLayer; the
+    published ``yolox_darknet.pth`` has this topology): the YoloFpn neck over Darknet-53 and a
+    256-wide LeakyReLU head on its 128 / 256 / 512-channel maps.  Eval-mode inference only."""
+    depth: float = 1.0
+    width: float = 1.0
+    act: Literal["silu", "relu", "lrelu"] = "lrelu"
+
+    def get_model(self):
+        from .models.network import YoloFpn, YoloxHead
+        from .models.yolox import YoloxModule
+
+        if self.model is None:
+            head = YoloxHead(self.num_classes, self.width, in_channels=[128, 256, 512], act="lrelu")
+            self.model = YoloxModule(YoloFpn(), head)
+        return super().get_model()  # BN eps / momentum, bias init, train mode
+
+
+_PRESETS["yolox_darknet"] = {}
+_PRESET_CLASS: dict[str, type] = {"yolox_darknet": YoloxDarknet}
+
+_NAMED_CONFIG: dict[str, YoloxConfig] = {n: _PRESET_CLASS.get(n, YoloxConfig)(n, **kw) for n, kw in _PRESETS.items()}
 
 
 def named_config(name: str) -> YoloxConfig:
@@ -312,4 +334,4 @@ def named_config(name: str) -> YoloxConfig:
     key = name.replace("-", "_")
     if key not in _PRESETS:
         raise ValueError(f"Unknown model: {name}")
-    return YoloxConfig(key, **_PRESETS[key])
+    return _PRESET_CLASS.get(key, YoloxConfig)(key, **_PRESETS[key])

@@ -87,6 +87,7 @@ class WeightSpec:
     kw: int
     cin_pad: int
     stem: bool = False  # fused Focus+stem layout [round16(cout)][6][32] (yxh_stem_pack)
+    rgb: bool = False  # RGB stem layout [round16(cout)][32] (yxh_rgb_stem_pack)
     w_off: int = -1  # bytes into weight arena
     b_off: int = -1  # bytes into bias arena
     f_off: int = -1  # bytes into the fragment-major copy (yxh_pack_frag), -1 = none
@@ -123,6 +124,9 @@ _WFRAG = os.environ.get("YOLOX_AMD_WFRAG", "1") != "0"
 # a head level's three preds + cat + sigmoid + decode as one head_pred launch (YOLOX_AMD_HEAD_PRED=0: the two
 # 1x1 pred convs with the fp32 decode epilogue, the form every level outside the launch's ranges takes)
 _HEAD_PRED = os.environ.get("YOLOX_AMD_HEAD_PRED", "1") != "0"
+# Darknet-53's first layer (3x3 s1 from the 3-channel image) as one yxh_rgb_stem_conv launch
+# (YOLOX_AMD_RGB_STEM=0: yxh_rgb_pack + the generic conv on 16 packed channels)
+_RGB_STEM = os.environ.get("YOLOX_AMD_RGB_STEM", "1") != "0"
 # feature widths head_pred2 is built for (head.hip): the six presets' head widths
 HEAD_PRED_WIDTHS = (64, 96, 128, 192, 256, 320)
 
@@ -141,6 +145,7 @@ class PlanCtx:
         self.device = device
         self.fuse_stem = fuse_stem
         self.fuse_stem_s2 = fuse_stem_s2  # Focus stem + dark2[0] as one yxh_stem_s2 launch
+        self.fuse_rgb_stem = fuse_stem and _RGB_STEM  # Darknet's RGB stem as one yxh_rgb_stem_conv launch
         # 1x1 convs folded into a neighbouring launch (stem_s2's CSP form; YOLOX_AMD_CSP_FUSION=0: off)
         self.csp_fusion = (_CSP_FUSION if csp_fusion is None else csp_fusion) and dtype != torch.float32
         # the image the plan reads (set by Plan): the fused stem + stride-2 conv needs NHWC
@@ -249,6 +254,31 @@ class PlanCtx:
         self.ops.append(OpRec(N.OP_FOCUS, dict(dst=packed.full(), h=h, w=w)))
         return packed.full()
 
+    def rgb_stem_fusable(self, m) -> bool:
+        c = m.conv
+        return (self.fuse_rgb_stem and c.in_channels == 3 and c.groups == 1 and c.kernel_size == (3, 3)
+                and c.stride == (1, 1) and c.padding == (1, 1) and c.bias is None
+                and c.out_channels % 16 == 0 and c.out_channels <= 64)
+
+    def rgb_stem(self, m, img: ImageRef) -> View:
+        """A BaseConv 3x3 s1 straight from the 3-channel image (darknet.py:31): one
+        yxh_rgb_stem_conv launch when the geometry fits, otherwise yxh_rgb_pack (16-channel
+        NHWC, 3 used) + the generic conv with its weights packed at cin_pad 16."""
+        conv = m.conv
+        if conv.in_channels != 3:
+            raise NotImplementedError(f"the image stem takes 3 channels, not {conv.in_channels}")
+        if not self.rgb_stem_fusable(m):
+            packed = self.buffer(img.h, img.w, 16)
+            self.ops.append(OpRec(N.OP_RGB_PACK, dict(dst=packed.full(), h=img.h, w=img.w)))
+            return self.conv(m, [packed.full()])
+        out = self.buffer(img.h, img.w, conv.out_channels)
+        spec = WeightSpec([(conv, m.bn)], conv.out_channels, 3, 3, 3, 3, rgb=True)
+        self.weights.append(spec)
+        self.ops.append(OpRec(N.OP_STEM_RGB, dict(dst=out.full(), h=img.h, w=img.w, spec=spec,
+                                                  act=N.ACT_CODE[getattr(m, "act_name", "silu")])))
+        self.flops += 2.0 * self.batch * out.h * out.w * conv.out_channels * 9 * 3
+        return out.full()
+
     def _weights(self, convs, cin_pad: int) -> WeightSpec:
         c0 = convs[0][0]
         spec = WeightSpec(convs, sum(c.out_channels for c, _ in convs), c0.in_channels // c0.groups,
@@ -279,7 +309,7 @@ class PlanCtx:
             raise ValueError("concatenated sources differ in spatial size")
         groups = conv.groups
         if groups == 1:
-            if conv.in_channels != cin and not (conv.in_channels == 12 and cin == 16):
+            if conv.in_channels != cin and not (conv.in_channels in (3, 12) and cin == 16):
                 raise ValueError(f"conv expects {conv.in_channels} channels, got {cin}")
         elif len(convs) > 1 or groups != cin or conv.out_channels != cin:
             raise NotImplementedError("only single depthwise grouped convs are supported")
@@ -528,7 +558,7 @@ def op_buffers(r: OpRec) -> tuple:
         return [a["buf"]], [a["buf"]]
     if r.kind == N.OP_STEM2 and a.get("dst") is None:
         return [], [a["dst3"].buf, a["dst4"].buf]
-    if r.kind in (N.OP_FOCUS, N.OP_STEM, N.OP_STEM2):
+    if r.kind in (N.OP_FOCUS, N.OP_STEM, N.OP_STEM2, N.OP_STEM_RGB, N.OP_RGB_PACK):
         return [], [a["dst"].buf]
     if r.kind == N.OP_HEAD:
         return [a["reg"].buf, a["cls"].buf], []
@@ -718,9 +748,9 @@ class Plan:
         for s in ctx.weights:
             s.w_off = woff
             s.b_off = boff
-            if s.stem:
+            if s.stem or s.rgb:
                 cpad = (s.cout + 15) // 16 * 16
-                woff += _align(cpad * 6 * 32 * ctx.esize)
+                woff += _align(cpad * (32 if s.rgb else 6 * 32) * ctx.esize)
                 boff += _align(cpad * 4)
             else:
                 woff += _align(s.cout * s.kh * s.kw * s.cin_pad * ctx.esize)
@@ -783,7 +813,7 @@ class Plan:
                 continue
             op = self._ops[c * self._nops + i]
             op.kind = rec.kind
-            if rec.kind == N.OP_FOCUS:
+            if rec.kind in (N.OP_FOCUS, N.OP_RGB_PACK):
                 f = op.u.focus
                 f.layout = self.input_layout
                 f.img_dtype = N.DTYPE_CODE[self.input_dtype]
@@ -792,7 +822,7 @@ class Plan:
                 f.dst = self._ptr(a["dst"], c)
                 f.img = None
                 self._input_index = i
-            elif rec.kind == N.OP_STEM:
+            elif rec.kind in (N.OP_STEM, N.OP_STEM_RGB):
                 t = op.u.stem
                 t.layout = self.input_layout
                 t.img_dtype = N.DTYPE_CODE[self.input_dtype]
@@ -967,13 +997,14 @@ class Plan:
                 keep.extend(a for a in args if a is not None)
                 eps = float(bn.eps) if bn is not None else 0.0
                 ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
-                if s.stem:
+                if s.stem or s.rgb:
                     if args[0] is not None:
                         raise NotImplementedError("fused stem conv with a conv bias")
-                    N.check(self.lib.yxh_stem_pack(
+                    pack = self.lib.yxh_rgb_stem_pack if s.rgb else self.lib.yxh_stem_pack
+                    N.check(pack(
                         w.data_ptr(), ptr(args[1]), ptr(args[2]), ptr(args[3]), ptr(args[4]), eps,
                         conv.out_channels, dt, self.warena.data_ptr() + s.w_off,
-                        self.barena.data_ptr() + s.b_off, stream), "stem_pack")
+                        self.barena.data_ptr() + s.b_off, stream), "rgb_stem_pack" if s.rgb else "stem_pack")
                     continue
                 wout = self.warena.data_ptr() + s.w_off + row * s.kh * s.kw * s.cin_pad * self.ctx.esize
                 bout = self.barena.data_ptr() + s.b_off + row * 4
@@ -1004,7 +1035,7 @@ class Plan:
         step = self.chunk * x[0].numel() * x.element_size()
         for c in range(self.nchunks):
             op = self._ops[c * self._nops + self._input_index]
-            if op.kind == N.OP_STEM:
+            if op.kind in (N.OP_STEM, N.OP_STEM_RGB):
                 op.u.stem.img = x.data_ptr() + c * step
             elif op.kind == N.OP_STEM2:
                 op.u.stem2.img = x.data_ptr() + c * step

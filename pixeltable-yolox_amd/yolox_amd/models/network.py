@@ -56,6 +56,7 @@ def _block_forward(block: nn.Module, x: torch.Tensor) -> list:
     a block plan: NCHW in, NCHW out in the parameters' dtype."""
     from .. import _native as N
     from ..engine import Plan
+    refuse_darknet_training(block)
     if not isinstance(x, torch.Tensor) or x.dim() != 4:
         raise ValueError(f"{type(block).__name__} takes one [B, C, H, W] tensor")
     p = _param0(block)
@@ -103,6 +104,18 @@ def _stage_plan(owner: nn.Module, key: tuple, make):
 
 def _param0(m: nn.Module) -> torch.Tensor:
     return next(m.parameters())
+
+
+def refuse_darknet_training(module: nn.Module) -> None:
+    """The Darknet-53 family (ResLayer, Darknet, YoloFpn) runs eval-mode inference only: a
+    train-mode forward of a model or block containing one raises here, before any device work."""
+    if not module.training:
+        return
+    for m in module.modules():
+        if isinstance(m, (ResLayer, Darknet, YoloFpn)):
+            raise NotImplementedError(
+                f"{type(m).__name__}: training the Darknet-53 family is not implemented (eval-mode "
+                f"inference only); call .eval() first")
 
 
 class BaseConv(_Planned):
@@ -437,6 +450,158 @@ class YoloPafpn(_Planned):
 
 def _out_channels(m: nn.Module) -> int:
     return m.pconv.conv.out_channels if isinstance(m, DWConv) else m.conv.out_channels
+
+
+class ResLayer(_Planned):
+    """Residual layer of Darknet (network_blocks.py:102-117): x + layer2(layer1(x)), a 1x1 to half
+    the channels and a 3x3 back, both LeakyReLU."""
+
+    def __init__(self, in_channels: int):
+        super().__init__()
+        mid = in_channels // 2
+        self.layer1 = BaseConv(in_channels, mid, ksize=1, stride=1, act="lrelu")
+        self.layer2 = BaseConv(mid, in_channels, ksize=3, stride=1, act="lrelu")
+
+    def plan(self, ctx, srcs, out=None):
+        """``out`` may alias the input (the residual is read and written pixel by pixel)."""
+        x = srcs[0]
+        t = self.layer1.plan(ctx, [x])
+        return self.layer2.plan(ctx, [t], out=out, residual=x)
+
+    def plan_block(self, ctx, x):
+        return self.plan(ctx, [x])
+
+
+def _plan_chain(ctx, blocks, x):
+    """A Sequential of BaseConv / ResLayer / SPPBottleneck over one map; ResLayers run in place
+    (every stage starts with a conv into a buffer of its own, so no feature map is overwritten)."""
+    for m in blocks:
+        x = m.plan(ctx, [x], out=x) if isinstance(m, ResLayer) else m.plan(ctx, [x])
+    return x
+
+
+class Darknet(_Planned):
+    """darknet.py:8-92: the Darknet-21 / -53 backbone.  The first layer reads the image directly
+    (PlanCtx.rgb_stem); everything else is the generic conv, one launch per BaseConv."""
+
+    depth2blocks = {21: [1, 2, 2, 1], 53: [2, 8, 8, 4]}  # ResLayers of dark2 .. dark5
+    FEATURES = ("stem", "dark2", "dark3", "dark4", "dark5")
+    takes_image = True
+
+    def __init__(self, depth, in_channels=3, stem_out_channels=32, out_features=("dark3", "dark4", "dark5")):
+        super().__init__()
+        assert out_features, "please provide output features of Darknet"
+        self.out_features = out_features
+        self.stem = nn.Sequential(BaseConv(in_channels, stem_out_channels, ksize=3, stride=1, act="lrelu"),
+                                  *self.make_group_layer(stem_out_channels, num_blocks=1, stride=2))
+        c = stem_out_channels * 2
+        n = Darknet.depth2blocks[depth]
+        self.dark2 = nn.Sequential(*self.make_group_layer(c, n[0], stride=2))
+        c *= 2
+        self.dark3 = nn.Sequential(*self.make_group_layer(c, n[1], stride=2))
+        c *= 2
+        self.dark4 = nn.Sequential(*self.make_group_layer(c, n[2], stride=2))
+        c *= 2
+        self.dark5 = nn.Sequential(*self.make_group_layer(c, n[3], stride=2),
+                                   *self.make_spp_block([c, c * 2], c * 2))
+
+    @staticmethod
+    def make_group_layer(in_channels: int, num_blocks: int, stride: int = 1) -> list:
+        return [BaseConv(in_channels, in_channels * 2, ksize=3, stride=stride, act="lrelu"),
+                *[ResLayer(in_channels * 2) for _ in range(num_blocks)]]
+
+    @staticmethod
+    def make_spp_block(filters_list, in_filters) -> nn.Sequential:
+        return nn.Sequential(BaseConv(in_filters, filters_list[0], 1, stride=1, act="lrelu"),
+                             BaseConv(filters_list[0], filters_list[1], 3, stride=1, act="lrelu"),
+                             SPPBottleneck(in_channels=filters_list[1], out_channels=filters_list[0],
+                                           activation="lrelu"),
+                             BaseConv(filters_list[0], filters_list[1], 3, stride=1, act="lrelu"),
+                             BaseConv(filters_list[1], filters_list[0], 1, stride=1, act="lrelu"))
+
+    def forward(self, x):
+        """darknet.py:80-92 standalone, eval mode: the requested feature maps of [B, 3, H, W] images
+        (NCHW, the parameters' dtype) as a dict in the reference's order."""
+        names = self._names()
+        return dict(zip(names, _block_forward(self, x)))
+
+    def _names(self) -> list:
+        if set(self.out_features) - set(self.FEATURES):
+            raise AttributeError(f"unknown out_features {self.out_features}")
+        return [k for k in self.FEATURES if k in self.out_features]
+
+    def plan_block(self, ctx, image):
+        outs = self.plan_all(ctx, image)
+        return [outs[k] for k in self._names()]
+
+    def plan(self, ctx, image):
+        outs = self.plan_all(ctx, image)
+        return outs["dark3"], outs["dark4"], outs["dark5"]
+
+    def plan_all(self, ctx, image) -> dict:
+        """{stem, dark2 .. dark5} maps."""
+        x = ctx.rgb_stem(self.stem[0], image)
+        outs = {"stem": _plan_chain(ctx, list(self.stem)[1:], x)}
+        x = outs["stem"]
+        for name in self.FEATURES[1:]:
+            x = outs[name] = _plan_chain(ctx, list(getattr(self, name)), x)
+        return outs
+
+
+class YoloFpn(_Planned):
+    """yolo_fpn.py:10-82: Darknet-53 with the two top-down YOLOv3 branches."""
+
+    def __init__(self, depth=53, in_features=("dark3", "dark4", "dark5")):
+        super().__init__()
+        self.backbone = Darknet(depth)
+        self.in_features = in_features
+        self.out1_cbl = self._make_cbl(512, 256, 1)
+        self.out1 = self._make_embedding([256, 512], 512 + 256)
+        self.out2_cbl = self._make_cbl(256, 128, 1)
+        self.out2 = self._make_embedding([128, 256], 256 + 128)
+        self.upsample = nn.Upsample(scale_factor=2, mode="nearest")
+
+    @staticmethod
+    def _make_cbl(_in, _out, ks) -> BaseConv:
+        return BaseConv(_in, _out, ks, stride=1, act="lrelu")
+
+    def _make_embedding(self, filters_list, in_filters) -> nn.Sequential:
+        a, b = filters_list
+        return nn.Sequential(self._make_cbl(in_filters, a, 1), self._make_cbl(a, b, 3), self._make_cbl(b, a, 1),
+                             self._make_cbl(a, b, 3), self._make_cbl(b, a, 1))
+
+    def forward(self, inputs):
+        """yolo_fpn.py:57-82 standalone, eval mode: [B, 3, H, W] images -> (out_dark3, out_dark4,
+        x0) NCHW in the parameters' dtype, computed by a features-only HIP plan."""
+        from .. import _native as N
+        from ..engine import Plan
+        refuse_darknet_training(self)
+        x = inputs
+        if x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"expected [B, 3, H, W] images, got {tuple(x.shape)}")
+        p = _param0(self)
+        if p.device.type != "cuda":
+            raise RuntimeError("YoloFpn runs on a ROCm device only; call .to('cuda') first")
+        if x.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.uint8):
+            x = x.float()
+        B, _, H, W = x.shape
+        key = ("features", B, H, W, x.dtype, p.dtype, str(p.device))
+        plan = _stage_plan(self, key, lambda: Plan(_StageModel(self, backbone=self), B, H, W, p.dtype, p.device,
+                                                   N.NCHW, x.dtype, stage="features"))
+        return plan.run_features(x)
+
+    def plan(self, ctx, image):
+        """Each torch.cat([upsample(x), skip]) is a two-source conv whose first source is read
+        at (y >> 1, x >> 1): no upsampled or concatenated map is materialised."""
+        outs = self.backbone.plan_all(ctx, image)
+        x2, x1, x0 = [outs[f] for f in self.in_features]
+        x1_in = self.out1_cbl.plan(ctx, [x0])
+        t = self.out1[0].plan(ctx, [x1_in.upsampled(), x1])
+        out_dark4 = _plan_chain(ctx, list(self.out1)[1:], t)
+        x2_in = self.out2_cbl.plan(ctx, [out_dark4])
+        t = self.out2[0].plan(ctx, [x2_in.upsampled(), x2])
+        out_dark3 = _plan_chain(ctx, list(self.out2)[1:], t)
+        return out_dark3, out_dark4, x0
 
 
 class YoloxHead(_Planned):

@@ -23,7 +23,7 @@ import torch.nn as nn
 
 from .. import _native as N
 from ..config import YoloxConfig, named_config
-from .network import YoloPafpn, YoloxHead
+from .network import YoloPafpn, YoloxHead, refuse_darknet_training
 from .processor import Detections, YoloxProcessor
 
 HOME = Path(os.environ.get("YOLOX_HOME", str(Path.home() / ".cache" / "yolox")))
@@ -107,13 +107,19 @@ class YoloxModule(nn.Module):
         return fold_master(self._masters, t)
 
     # ---------------------------------------------------------------- execution
+    def _stem_weight(self) -> torch.Tensor:
+        """The first conv's weight: the Focus stem's (CspDarknet) or stem[0]'s (Darknet)."""
+        stem = self.backbone.backbone.stem
+        first = stem[0] if isinstance(stem, nn.Sequential) else stem.conv
+        return first.conv.weight
+
     @property
     def compute_dtype(self) -> torch.dtype:
-        return self.backbone.backbone.stem.conv.conv.weight.dtype
+        return self._stem_weight().dtype
 
     @property
     def device(self) -> torch.device:
-        return self.backbone.backbone.stem.conv.conv.weight.device
+        return self._stem_weight().device
 
     def plan_for(self, batch: int, height: int, width: int, input_layout: int = N.NCHW,
                  input_dtype: torch.dtype = torch.float32, dtype: Optional[torch.dtype] = None,
@@ -137,6 +143,7 @@ class YoloxModule(nn.Module):
 
     def forward(self, x, targets=None):
         if self.training:
+            refuse_darknet_training(self)
             # yolox.py:76-87: loss dict; BN batch statistics, on-device SimOTA, HIP
             # reverse pass behind total_loss.backward() (yolox_amd/train.py)
             assert targets is not None

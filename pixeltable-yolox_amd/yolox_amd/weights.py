@@ -77,8 +77,25 @@ def _tensor_for(key: str, shape: Sequence[int], seed: int) -> torch.Tensor:
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
 
 
+def bn_stats_dirs() -> list[str]:
+    """Where ``bn_stats_<model>.npz`` tables are looked for, in order: the package's ``data/``, the
+    directory ``YOLOX_AMD_BN_STATS_DIR`` names, and the source tree's ``tests/golden/`` (tables kept with
+    the fixtures they were generated with: yolox_darknet's)."""
+    dirs = [DATA_DIR]
+    if os.environ.get("YOLOX_AMD_BN_STATS_DIR"):
+        dirs.append(os.environ["YOLOX_AMD_BN_STATS_DIR"])
+    tree = os.path.dirname(os.path.dirname(os.path.dirname(DATA_DIR)))
+    dirs.append(os.path.join(tree, "tests", "golden"))
+    return dirs
+
+
 def load_bn_stats(model_name: str) -> dict[str, torch.Tensor]:
-    path = os.path.join(DATA_DIR, f"bn_stats_{model_name}.npz")
+    name = f"bn_stats_{model_name}.npz"
+    path = next((p for p in (os.path.join(d, name) for d in bn_stats_dirs()) if os.path.isfile(p)), None)
+    if path is None:
+        raise FileNotFoundError(f"{name} not found in {bn_stats_dirs()}: the calibrated BN statistics of synthetic "
+                                f"weights ship in the package's data/ or, for yolox_darknet, with the source "
+                                f"tree's tests/golden/ fixtures (set YOLOX_AMD_BN_STATS_DIR to their directory)")
     with np.load(path) as z:
         return {k: torch.from_numpy(np.array(z[k])) for k in z.files}
 
