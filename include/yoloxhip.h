@@ -575,9 +575,13 @@ int yxh_channel_sum(int32_t dtype, int32_t batch, const yxh_src* x, float* out, 
 /*
  * yxh_conv_wgrad: weight gradient of Conv2d (autograd of network_blocks.py:48 and the
  * head's preds, yolo_head.py:149-160) on MFMA: dw[cout][cin_store][kh][kw] (torch layout,
- * fp32) += sum over output pixels of dy[cout] * x[cin](tap).  dw must be zeroed by the
- * caller (split-K over pixel ranges with fp32 atomics).  src: the forward's input views
- * (1-2 sources, nearest-x2 allowed); dy.channels >= cout, padded to 16-byte chunks.
+ * fp32) += sum over output pixels of dy[cout] * x[cin](tap).  The sum is ADDED onto what dw
+ * holds, on every tile and with or without a workspace (split-K over pixel ranges: fp32
+ * atomics, or per-split partials summed and added by a second launch), so the caller zeroes
+ * dw for a fresh gradient; nothing outside dw's cout * cin_store * kh * kw floats is written.
+ * src: the forward's input views (1-2 sources, nearest-x2 allowed); dy.channels >= cout,
+ * padded to 16-byte chunks (a tile may read dy's pad channels [cout, dy.channels), never use
+ * them; it reads nothing outside the views).
  */
 typedef struct {
     int32_t dtype, batch, in_h, in_w, out_h, out_w, cin, cout, kh, kw, stride, pad;
