@@ -403,6 +403,72 @@ int yxh_resize_u8_batch(const uint8_t* src, const yxh_resize_image* images, int3
 size_t yxh_sizeof_resize_image(void);
 
 /*
+ * Baseline JPEG decoding, split where the work changes character: the Huffman decode is serial and
+ * stays on the host (csrc/jpeg_host.cpp: plain C++, no device, thread-safe, no global state);
+ * dequantisation, the 8x8 IDCT, chroma upsampling and YCbCr -> RGB are dense integer arithmetic
+ * over independent blocks and run on the device (csrc/jpeg.hip).  The result is libjpeg-turbo's
+ * default decode (islow IDCT, fancy upsampling) byte for byte: packed uint8 H x W x 3 RGB, what
+ * np.asarray(PIL image.convert("RGB")) gives and what yxh_letterbox_batch / yxh_resize_u8_batch read.
+ *
+ * Subset: SOF0, 8-bit, one interleaved scan; one component, or three with luma sampling 1x1, 2x1 or
+ * 2x2 over 1x1 chroma; any restart interval; JFIF, or no Adobe marker (an Adobe marker that says
+ * YCbCr is taken too).  Any other valid file -- progressive, arithmetic, 12-bit, CMYK / YCCK, Adobe
+ * transform 0, 4:4:0, 4:1:1, several scans, 16-bit quantisation tables -- is YXH_EUNSUPPORTED with
+ * the reason in yxh_last_error(); bytes that are no well-formed JPEG, and any Huffman or marker
+ * error in the scan, are YXH_EINVAL (there is no corrupt-data recovery).
+ *
+ * yxh_jpeg_probe reads the headers up to the scan and writes `info` only.  yxh_jpeg_decode fills
+ * the caller's `coef` (at least info.coef_bytes; in practice pinned memory) with the quantised
+ * coefficients as int16: 64 per block in natural (de-zigzagged) order, component after component,
+ * each component's blocks row by row, block rows padded to whole MCUs; and `image` with the sizes
+ * and the quantisation tables (its three offsets are left 0 for the caller to set).  Neither reads
+ * past `len` or writes outside `coef_bytes`.
+ *
+ * yxh_jpeg_render_batch renders a ragged batch in one call on `stream`: `coef`, `images` (device,
+ * one descriptor per image), `workspace` and `dst` are device memory; image i reads its
+ * coefficients at coef + coef_offset, uses yxh_jpeg_workspace_bytes(height, width, sampling) bytes
+ * of `workspace` at ws_offset for its component planes and writes exactly
+ * [dst_offset, dst_offset + height*width*3) of `dst`, at any byte alignment.  coef_offset and
+ * ws_offset are multiples of 16, `coef` and `workspace` 16-byte aligned; a descriptor that breaks
+ * this or has impossible sizes is skipped whole.  The caller checks that every range lies inside
+ * its buffers.  Like every device entry it neither allocates nor synchronises.
+ * yxh_jpeg_render_host is the same arithmetic (csrc/jpeg_math.hpp, shared by both) as scalar host
+ * code over host pointers: the CPU-testable statement of it.
+ *
+ * Added without a new YXH_ABI_VERSION, as yxh_resize_u8_batch was: the entries are additive, and
+ * yxh_sizeof_jpeg_info / yxh_sizeof_jpeg_image are the layout self-checks for bindings.
+ */
+enum yxh_jpeg_sampling { YXH_JPEG_GRAY = 0, YXH_JPEG_444 = 1, YXH_JPEG_422 = 2, YXH_JPEG_420 = 3 };
+typedef struct {
+    int32_t height, width;
+    int32_t components;  /* 1 or 3 */
+    int32_t sampling;    /* yxh_jpeg_sampling */
+    int64_t coef_bytes;  /* the coefficient buffer yxh_jpeg_decode needs */
+} yxh_jpeg_info;
+typedef struct {
+    int64_t coef_offset;  /* bytes into coef, a multiple of 16 (caller-set) */
+    int64_t dst_offset;   /* bytes into dst, any alignment (caller-set) */
+    int64_t ws_offset;    /* bytes into workspace, a multiple of 16 (caller-set) */
+    int32_t height, width;
+    int32_t components;
+    int32_t sampling;
+    int32_t blocks_w[3], blocks_h[3]; /* per component, padded to whole MCUs (informational: the
+                                         render stage derives them from the four fields above) */
+    int32_t comp_block0[3];           /* first block of each component behind coef_offset */
+    int32_t reserved;
+    uint16_t quant[3][64];            /* per component, natural order */
+} yxh_jpeg_image;
+int yxh_jpeg_probe(const uint8_t* data, size_t len, yxh_jpeg_info* info);
+int yxh_jpeg_decode(const uint8_t* data, size_t len, int16_t* coef, size_t coef_bytes, yxh_jpeg_image* image);
+size_t yxh_jpeg_workspace_bytes(int32_t height, int32_t width, int32_t sampling);
+int yxh_jpeg_render_host(const int16_t* coef, const yxh_jpeg_image* images, int32_t batch, uint8_t* workspace,
+                         uint8_t* dst);
+int yxh_jpeg_render_batch(const int16_t* coef, const yxh_jpeg_image* images, int32_t batch, uint8_t* workspace,
+                          uint8_t* dst, void* stream);
+size_t yxh_sizeof_jpeg_info(void);
+size_t yxh_sizeof_jpeg_image(void);
+
+/*
  * yxh_postprocess: utils.postprocess (utils/boxes.py:31-75) with torchvision
  * nms / batched_nms semantics (CPU branch rule: boxes.numel() > vanilla_numel ->
  * per-class NMS, else coordinate-offset NMS) on device.

@@ -74,6 +74,8 @@ int letterbox_batch_launch(const uint8_t* pool, const yxh_lb_image* images, int 
                            void* dst, hipStream_t st);
 int resize_u8_batch_launch(const uint8_t* src, const yxh_resize_image* images, int B, int flags, uint8_t* dst,
                            hipStream_t st);
+int jpeg_render_launch(const int16_t* coef, const yxh_jpeg_image* images, int B, uint8_t* workspace, uint8_t* dst,
+                       hipStream_t st);
 size_t reduce_workspace(int C);
 int bn_stats(int dt, int B, const yxh_src* y, const float* gamma, const float* beta, float* rmean, float* rvar,
              float eps, float momentum, float* stats, void* ws, size_t ws_bytes, hipStream_t st);
@@ -231,6 +233,12 @@ int yxh_resize_u8_batch(const uint8_t* src, const yxh_resize_image* images, int3
 }
 
 size_t yxh_sizeof_resize_image(void) { return sizeof(yxh_resize_image); }
+
+// yxh_jpeg_probe / _decode / _render_host / _workspace_bytes and the sizeof checks: csrc/jpeg_host.cpp
+int yxh_jpeg_render_batch(const int16_t* coef, const yxh_jpeg_image* images, int32_t batch, uint8_t* workspace,
+                          uint8_t* dst, void* stream) {
+    return jpeg_render_launch(coef, images, batch, workspace, dst, (hipStream_t)stream);
+}
 
 size_t yxh_postprocess_workspace_bytes(int32_t batch, int32_t anchors) { return pp_workspace(batch, anchors); }
 

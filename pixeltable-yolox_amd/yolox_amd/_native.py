@@ -148,6 +148,23 @@ class ResizeImage(C.Structure):
                 ("dst_h", C.c_int32), ("dst_w", C.c_int32)]
 
 
+JPEG_GRAY, JPEG_444, JPEG_422, JPEG_420 = 0, 1, 2, 3
+
+
+class JpegInfo(C.Structure):
+    """yxh_jpeg_info (include/yoloxhip.h): what yxh_jpeg_probe reports."""
+    _fields_ = [("height", C.c_int32), ("width", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
+                ("coef_bytes", C.c_int64)]
+
+
+class JpegImage(C.Structure):
+    """yxh_jpeg_image (include/yoloxhip.h): one image of a yxh_jpeg_render_batch launch."""
+    _fields_ = [("coef_offset", C.c_int64), ("dst_offset", C.c_int64), ("ws_offset", C.c_int64),
+                ("height", C.c_int32), ("width", C.c_int32), ("components", C.c_int32), ("sampling", C.c_int32),
+                ("blocks_w", C.c_int32 * 3), ("blocks_h", C.c_int32 * 3), ("comp_block0", C.c_int32 * 3),
+                ("reserved", C.c_int32), ("quant", (C.c_uint16 * 64) * 3)]
+
+
 class HeadDesc(C.Structure):
     _fields_ = [("dtype", C.c_int32), ("batch", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("cin", C.c_int32),
                 ("num_classes", C.c_int32), ("reg", Src), ("cls", Src), ("w_reg", C.c_void_p), ("b_reg", C.c_void_p),
@@ -222,6 +239,13 @@ def lib():
             "yxh_sizeof_aug_image": ([], sz),
             "yxh_resize_u8_batch": ([vp, vp, i32, i32, vp, vp], C.c_int),
             "yxh_sizeof_resize_image": ([], sz),
+            "yxh_jpeg_probe": ([vp, sz, C.POINTER(JpegInfo)], C.c_int),
+            "yxh_jpeg_decode": ([vp, sz, vp, sz, C.POINTER(JpegImage)], C.c_int),
+            "yxh_jpeg_workspace_bytes": ([i32, i32, i32], sz),
+            "yxh_jpeg_render_host": ([vp, vp, i32, vp, vp], C.c_int),
+            "yxh_jpeg_render_batch": ([vp, vp, i32, vp, vp, vp], C.c_int),
+            "yxh_sizeof_jpeg_info": ([], sz),
+            "yxh_sizeof_jpeg_image": ([], sz),
             "yxh_postprocess_workspace_bytes": ([i32, i32], sz),
             "yxh_set_nms_mask_budget": ([sz], None),
             "yxh_postprocess": ([vp, i32, i32, i32, f32, f64, i32, i64, vp, vp, vp, sz, vp], C.c_int),
@@ -283,7 +307,9 @@ def lib():
             raise NativeError(f"ABI mismatch: library {L.yxh_abi_version()} vs binding {ABI_VERSION}")
         if (L.yxh_sizeof_op() != C.sizeof(Op) or L.yxh_sizeof_conv_desc() != C.sizeof(ConvDesc)
                 or L.yxh_sizeof_aug_image() != C.sizeof(AugImage)
-                or L.yxh_sizeof_resize_image() != C.sizeof(ResizeImage)):
+                or L.yxh_sizeof_resize_image() != C.sizeof(ResizeImage)
+                or L.yxh_sizeof_jpeg_info() != C.sizeof(JpegInfo)
+                or L.yxh_sizeof_jpeg_image() != C.sizeof(JpegImage)):
             raise NativeError("struct layout mismatch between yoloxhip.h and _native.py")
         _lib = L
     return _lib
@@ -299,7 +325,9 @@ EXPORTED = ["yxh_abi_version", "yxh_last_error", "yxh_sizeof_op", "yxh_sizeof_co
             "yxh_yolox_loss_ex", "yxh_yolox_loss_bwd_ex", "yxh_iou_loss_workspace_bytes", "yxh_iou_loss", "yxh_iou_loss_bwd",
             "yxh_sgd_ema_step", "yxh_amp_found_inf", "yxh_amp_update_scale", "yxh_coco_eval", "yxh_coco_iou",
             "yxh_resize_u8_batch", "yxh_sizeof_resize_image",
-            "yxh_rgb_stem_pack", "yxh_rgb_stem_conv", "yxh_rgb_pack"]
+            "yxh_rgb_stem_pack", "yxh_rgb_stem_conv", "yxh_rgb_pack",
+            "yxh_jpeg_probe", "yxh_jpeg_decode", "yxh_jpeg_workspace_bytes", "yxh_jpeg_render_host",
+            "yxh_jpeg_render_batch", "yxh_sizeof_jpeg_info", "yxh_sizeof_jpeg_image"]
 
 
 def check(rc: int, what: str = "") -> None:

@@ -7,11 +7,15 @@ construction decodes nothing and the random draws do not depend on what is cache
 runs before a render: the batch's missing images are decoded as RGB at their original size in a
 thread pool (PIL releases the GIL in the decoder), packed into pinned staging, uploaded, and one
 ``yxh_resize_u8_batch`` launch resizes them -- swapping to BGR on the way -- into fixed-size
-slots, on the stream the render uses.  Slots are ``align16(H * W * 3)`` bytes of ``img_size``:
-a resized image never exceeds it, eviction is a table update and the pool never fragments.
+slots, on the stream the render uses.  With the device JPEG path on (``yolox_amd.jpeg``,
+``YOLOX_AMD_JPEG``), a baseline JPEG whose EXIF orientation is 1 skips PIL: its Huffman decode runs
+in the decoder's thread pool into the pinned staging, ``yxh_jpeg_render_batch`` turns the
+coefficients into the same RGB bytes on the device, and the same resize follows.  Slots are
+``align16(H * W * 3)`` bytes of ``img_size``: a resized image never exceeds it, eviction is a table update and the pool never fragments.
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 from collections import OrderedDict
 from concurrent.futures import ThreadPoolExecutor
@@ -115,6 +119,8 @@ class StreamedImages:
         self.workers = min(16, max(1, int(workers)))
         self.staging_bytes = int(staging_bytes)
         self._host = self._dev = None
+        from ..jpeg import JpegDecoder
+        self.jpeg = JpegDecoder(workers=self.workers)  # .stats: files rendered on the device / handed to PIL
         # RGB from the decoder and the swap on the device; a dataset without load_rgb gives BGR as is
         self._decode, self._swap = ((dataset.load_rgb, True) if hasattr(dataset, "load_rgb")
                                     else (dataset.load_image, False))
@@ -139,7 +145,9 @@ class StreamedImages:
         h, w = self.infos[i]
         return int(h) * int(w) * 3
 
-    def _staging(self, nbytes: int):
+    def _staging(self, nbytes: int, dev_bytes: int = 0):
+        """Pinned staging of ``nbytes`` and its device copy, which may be asked for more
+        (``dev_bytes``: what only the device writes, behind the copied range)."""
         import torch
         if self._host is None or self._host.numel() < nbytes:
             have = 0 if self._host is None else self._host.numel()
@@ -147,7 +155,10 @@ class StreamedImages:
             self._host = torch.empty(nbytes, dtype=torch.uint8)
             if self.device.type == "cuda":
                 self._host = self._host.pin_memory()
-            self._dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+            self._dev = None
+        need = max(self._host.numel(), dev_bytes)
+        if self._dev is None or self._dev.numel() < need:
+            self._dev = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._host, self._dev
 
     def ensure(self, indices: Iterable[int]) -> None:
@@ -171,29 +182,87 @@ class StreamedImages:
             self.table.drop(lost)
             raise
 
-    def _load(self, items, nbytes: int) -> None:
-        """One copy + launch round: decode ``items`` [(image, slot)], upload, resize into the slots."""
+    def _prepare(self, i: int):
+        """One missing image for ``_load``: an ``Encoded`` JPEG the device decoder takes (grayscale
+        included, which ``convert("RGB")`` replicates; not a file whose EXIF orientation PIL would
+        apply), checked against the annotation file like ``load_rgb`` -- or ``load_rgb``'s array."""
+        path = self.dataset.image_path(i)
+        if not os.path.isfile(path):
+            raise FileNotFoundError(f"file named {path} not found")
+        e = self.jpeg.accept(self.jpeg.read(path), gray=True, exif=True)
+        if e is None:
+            return self._decode(i)
+        height, width = (int(v) for v in self.infos[i])
+        if (e.height, e.width) != (height, width):
+            raise ValueError(f"{path} decodes to {e.height}x{e.width}, the annotation file says "
+                             f"{height}x{width}")
+        return e
+
+    def _load(self, items, nbytes: int, pil_only=frozenset()) -> None:
+        """One copy + launch round: decode ``items`` [(image, slot)], upload, resize into the slots.
+        ``pil_only``: images the entropy decoder refused in a first attempt."""
         from .. import _native as N
+        from ..jpeg import Encoded, render_batch
         from .coco import resize_u8_batch
-        host, dev = self._staging(nbytes)
         images = [i for i, _ in items]
+        on_device = self.jpeg.on and hasattr(self.dataset, "image_path") and hasattr(self.dataset, "load_rgb")
+
+        def fetch(i):
+            return self._prepare(i) if on_device and i not in pil_only else self._decode(i)
+
         if self.workers > 1 and len(images) > 1:
             with ThreadPoolExecutor(min(self.workers, len(images))) as ex:
-                decoded = list(ex.map(self._decode, images))
+                decoded = list(ex.map(fetch, images))
         else:
-            decoded = [self._decode(i) for i in images]
-        view = host.numpy()
-        descs, off = [], 0
+            decoded = [fetch(i) for i in images]
+        # copied range: decoded pixels or coefficients per image, then the JPEG descriptors; behind
+        # it on the device only: the regions the JPEGs are rendered into and the plane workspace
+        src, off = [], 0
         for (i, slot), img in zip(items, decoded):
+            src.append(off)
+            if isinstance(img, Encoded):
+                off += _align16(img.coef_bytes)
+                continue
             h, w = (int(v) for v in self.infos[i])
             if img.shape != (h, w, 3) or img.dtype != np.uint8:
                 raise ValueError(f"image {i} decodes to {img.shape} {img.dtype}, the annotation file says "
                                  f"{h}x{w}x3 uint8")
-            view[off:off + img.size] = img.reshape(-1)
-            rh, rw = (int(v) for v in self.shapes[i])
-            descs.append(N.ResizeImage(off, slot * self.slot_bytes, h, w, rh, rw))
             off += _align16(img.size)
+        enc = [k for k, img in enumerate(decoded) if isinstance(img, Encoded)]
+        jdesc_off = off
+        nbytes = off = jdesc_off + C.sizeof(N.JpegImage) * len(enc)
+        off = _align16(off)
+        rgb, ws = {}, {}
+        for k in enc:
+            rgb[k] = off
+            off += _align16(decoded[k].rgb_bytes)
+        for k in enc:
+            ws[k] = off
+            off += decoded[k].workspace_bytes
+        host, dev = self._staging(nbytes, off)
+        view = host.numpy()
+        if enc:
+            res = self.jpeg.decode([decoded[k] for k in enc], host.data_ptr(), [src[k] for k in enc])
+            refused = {images[k] for k, (_, err) in zip(enc, res) if err is not None}
+            if refused:  # PIL takes them (and raises on them, if it must, as it always did)
+                self.jpeg.stats["device"] -= len(enc) - len(refused)
+                return self._load(items, nbytes, pil_only | refused)
+            jd = (N.JpegImage * len(enc))()
+            for j, (k, (image, _)) in enumerate(zip(enc, res)):
+                image.coef_offset, image.dst_offset, image.ws_offset = src[k], rgb[k], ws[k]
+                jd[j] = image
+            view[jdesc_off:nbytes] = np.frombuffer(jd, np.uint8)
+        descs = []
+        for k, ((i, slot), img) in enumerate(zip(items, decoded)):
+            h, w = (int(v) for v in self.infos[i])
+            if not isinstance(img, Encoded):
+                view[src[k]:src[k] + img.size] = img.reshape(-1)
+            rh, rw = (int(v) for v in self.shapes[i])
+            descs.append(N.ResizeImage(rgb.get(k, src[k]), slot * self.slot_bytes, h, w, rh, rw))
         dev[:nbytes].copy_(host[:nbytes], non_blocking=False)  # staging is free again when this returns
+        if enc:
+            p = dev.data_ptr()
+            render_batch(p, p + jdesc_off, len(enc), p, p, N.stream_ptr(self.device))
         resize_u8_batch(dev, descs, self.pool, swap_rb=self._swap)
         for (i, slot) in items:
             self.offsets[i] = slot * self.slot_bytes

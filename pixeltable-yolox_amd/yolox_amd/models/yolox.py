@@ -261,6 +261,16 @@ class Yolox:
         self.processor = processor
         self._pipelines: dict = {}  # yolox_amd.serve.Pipeline per (device, dtype, batch size, test size)
         self._streaming = False
+        self._jpeg = None
+
+    @property
+    def jpeg(self):
+        """The ``yolox_amd.jpeg.JpegDecoder`` every pipeline of this object shares: its ``stats``
+        say how many files ``stream`` rendered on the device and how many it handed to PIL, and why."""
+        if self._jpeg is None:
+            from ..jpeg import JpegDecoder
+            self._jpeg = JpegDecoder(workers=16)
+        return self._jpeg
 
     @classmethod
     def from_pretrained(cls, pretrained_model_name_or_path: Union[str, os.PathLike],
@@ -294,15 +304,18 @@ class Yolox:
         self._pipelines = {k: p for k, p in self._pipelines.items() if k[:2] == key[:2] and p.module is m}
         pipe = self._pipelines.get(key)
         if pipe is None:
-            pipe = self._pipelines[key] = Pipeline(m, self.processor, batch_size, tune=tune)
+            pipe = self._pipelines[key] = Pipeline(m, self.processor, batch_size, tune=tune, jpeg=self.jpeg)
         return pipe
 
     def stream(self, inputs: Iterable, threshold: float = 0.5, batch_size: int = 32) -> Iterator[Detections]:
         """One ``Detections`` per input, in input order, from the pipelined serving path
         (yolox_amd.serve.Pipeline): batches of ``batch_size`` go through a captured forward, the
         device NMS and ``yxh_detections_pack`` while the host packs the next batch and formats the
-        last one.  ``inputs``: what ``__call__`` accepts (paths, PIL images) and H x W x 3 uint8 RGB
-        arrays, from any iterable -- it is read lazily, at most two batches ahead of the results.
+        last one.  ``inputs``: what ``__call__`` accepts (paths, PIL images), encoded images as
+        ``bytes`` / ``bytearray`` / ``memoryview``, and H x W x 3 uint8 RGB arrays, from any iterable
+        -- it is read lazily, at most two batches ahead of the results.  With ``YOLOX_AMD_JPEG=1`` a
+        path or bytes holding a baseline JPEG is decoded on the device (``yolox_amd.jpeg``; the same
+        bytes as PIL's, so the same detections); everything else goes through PIL as before.
         An input the reference rejects (grayscale, RGBA, empty) raises ValueError when its batch is
         packed.  One stream per ``Yolox`` at a time: a second concurrent one raises RuntimeError;
         closing or exhausting the generator releases it."""

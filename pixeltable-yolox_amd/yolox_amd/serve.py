@@ -4,8 +4,11 @@
 
 * the host packs the image bytes, the letterbox descriptors and the fp32 letterbox ratios into one
   of two pinned staging slots, and one H2D copy on a copy stream moves them -- while the batch
-  before runs;
-* on the forward stream: the letterbox straight into the captured plan's input, ``plan.replay()``,
+  before runs.  An input that is a path or encoded bytes and a baseline JPEG the device decoder
+  takes (``yolox_amd.jpeg``) is not decoded on the host: its Huffman decode runs on a thread pool
+  straight into the staging slot, coefficients instead of pixels;
+* on the forward stream: ``yxh_jpeg_render_batch`` of those coefficients into the pool regions the
+  letterbox descriptors point at, the letterbox straight into the captured plan's input, ``plan.replay()``,
   the NMS filter (fed by the head's score records where the plan emits them);
 * on a side stream, beside the next batch's forward: the rest of the NMS, ``yxh_detections_pack``
   (boxes divided by the ratio, rows compacted over the batch), one D2H of the offsets plus the first
@@ -19,6 +22,8 @@ submitted: that ordering is what keeps every double buffer safe.
 """
 from __future__ import annotations
 
+import ctypes
+import io
 import os
 from collections import deque
 from itertools import islice
@@ -29,10 +34,12 @@ import torch
 
 from . import _native as N
 from .engine import Plan
+from .jpeg import Encoded, JpegDecoder, render_batch
 from .models.processor import Detections, letterbox_fill, letterbox_layout
 from .utils.boxes import _Workspace, postprocess_device
 
 ROW_BYTES = 32  # yxh_detections_pack's record
+C_SIZEOF_JPEG_IMAGE = ctypes.sizeof(N.JpegImage)  # yxh_jpeg_image (N.lib() checks it against the library)
 
 
 def format_detections(rows: np.ndarray, offsets, n: int) -> list[Detections]:
@@ -53,16 +60,26 @@ def format_detections(rows: np.ndarray, offsets, n: int) -> list[Detections]:
     return out
 
 
+ENCODED_TYPES = (bytes, bytearray, memoryview)  # an encoded image held in memory
+
+
 def as_array(im) -> np.ndarray:
-    """One input of ``Yolox.stream``: a path, a PIL image or an H x W x 3 uint8 array -> the array
-    (as-is, like the reference's ``np.array(image)``: nothing is converted to RGB)."""
+    """One input of ``Yolox.stream``: a path, the bytes of an encoded image, a PIL image or an
+    H x W x 3 uint8 array -> the array (as-is, like the reference's ``np.array(image)``: nothing is
+    converted to RGB)."""
     if isinstance(im, np.ndarray):
         return im
-    if isinstance(im, (str, os.PathLike)):
+    if isinstance(im, ENCODED_TYPES):
+        im = io.BytesIO(im)
+    if isinstance(im, (str, os.PathLike, io.BytesIO)):
         from PIL import Image
         with Image.open(im) as f:
             return np.asarray(f)
     return np.asarray(im)
+
+
+def _align16(n: int) -> int:
+    return (n + 15) & ~15
 
 
 class _Slot:
@@ -82,16 +99,21 @@ class _Slot:
         self.done = torch.cuda.Event()
         self.n = 0
 
-    def staging(self, nbytes: int, device) -> None:
+    def staging(self, nbytes: int, device, dev_bytes: int = 0) -> None:
+        """Room for ``nbytes`` of staging and its device copy; the device side may be asked for more
+        (``dev_bytes``: regions only the device writes, behind the copied range)."""
         if self.host is None or self.host.numel() < nbytes:
             size = max(nbytes, 1 << 20) * 5 // 4
             self.host = torch.empty(size, dtype=torch.uint8, pin_memory=True)
-            self.pool = torch.empty(size, dtype=torch.uint8, device=device)
+        need = max(self.host.numel(), dev_bytes)
+        if self.pool is None or self.pool.numel() < need:
+            self.pool = torch.empty(need if need == self.host.numel() else need * 5 // 4, dtype=torch.uint8,
+                                    device=device)
 
 
 class Pipeline:
     def __init__(self, module, processor, batch_size: int, capacity_rows: Optional[int] = None,
-                 tune: bool = False):
+                 tune: bool = False, jpeg: Optional[JpegDecoder] = None):
         if batch_size < 1:
             raise ValueError(f"batch_size must be positive, got {batch_size}")
         if module.device.type != "cuda":
@@ -122,6 +144,7 @@ class Pipeline:
                 s.workspace.buf = torch.zeros(int(self.lib.yxh_postprocess_workspace_bytes(B, A)), dtype=torch.uint8,
                                               device=self.device)
             torch.cuda.synchronize(self.device)  # the fills above ran on the caller's stream
+        self.jpeg = jpeg if jpeg is not None else JpegDecoder(workers=16)
         self.k = 0
         self.inflight: deque = deque()
 
@@ -134,10 +157,13 @@ class Pipeline:
 
     def pack(self, slot: _Slot, arrays: list) -> tuple:
         """Host half of a batch: the image bytes, the letterbox descriptors and the fp32 ratios into the
-        slot's pinned staging.  Returns (n, descriptor offset, ratio offset, total bytes)."""
+        slot's pinned staging.  Returns (n, descriptor offset, ratio offset, total bytes, JPEG part);
+        the last is None unless the batch holds ``Encoded`` items (``pack_encoded``)."""
         B, (th, tw) = self.batch, self.size
         n = len(arrays)
         assert 0 < n <= B
+        if any(isinstance(a, Encoded) for a in arrays):
+            return self.pack_encoded(slot, list(arrays))
         arrays, offs, desc_off = letterbox_layout(arrays, self.size)  # ValueError: nothing launched yet
         ratio_off = desc_off + 16 * n
         total = ratio_off + 4 * B
@@ -147,12 +173,80 @@ class Pipeline:
         ratios = np.ones(B, np.float32)  # Python double, rounded once to fp32 (processor.py:45-49)
         ratios[:n] = [min(th / a.shape[0], tw / a.shape[1]) for a in arrays]
         hn[ratio_off:total] = ratios.view(np.uint8)
-        return n, desc_off, ratio_off, total
+        return n, desc_off, ratio_off, total, None
+
+    def pack_encoded(self, slot: _Slot, items: list) -> tuple:
+        """``pack`` for a batch that mixes arrays and ``Encoded`` JPEGs, in input order.  Copied
+        range of the slot: array pixels, letterbox descriptors, ratios, JPEG descriptors,
+        coefficients; behind it, on the device only: the regions the JPEGs are rendered into (what
+        their letterbox descriptors point at) and the component-plane workspace."""
+        B, (th, tw) = self.batch, self.size
+        n = len(items)
+        enc = [k for k, a in enumerate(items) if isinstance(a, Encoded)]
+        plain = [k for k in range(n) if not isinstance(items[k], Encoded)]
+        if plain:  # the reference's checks, ValueError before anything is launched
+            for k, a in zip(plain, letterbox_layout([items[k] for k in plain], self.size)[0]):
+                items[k] = a
+        for k in enc:
+            e = items[k]
+            r = min(th / e.height, tw / e.width)
+            if int(e.width * r) <= 0 or int(e.height * r) <= 0:
+                raise ValueError(f"image {(e.height, e.width)} resizes to nothing at {self.size}")
+        m = len(enc)
+        src, off = [0] * n, 0
+        for k in plain:
+            src[k] = off
+            off += _align16(items[k].nbytes)
+        desc_off = off
+        ratio_off = desc_off + 16 * n
+        jdesc_off = _align16(ratio_off + 4 * B)
+        off = jdesc_off + C_SIZEOF_JPEG_IMAGE * m
+        coef = []
+        for k in enc:
+            coef.append(off)
+            off += _align16(items[k].coef_bytes)
+        total = off
+        ws = []
+        for k in enc:  # device-only regions
+            src[k] = off
+            off += _align16(items[k].rgb_bytes)
+        for k in enc:
+            ws.append(off)
+            off += items[k].workspace_bytes
+        slot.staging(total, self.device, off)
+        hn = slot.host.numpy()
+        decoded = self.jpeg.decode([items[k] for k in enc], slot.host.data_ptr(), coef)
+        if any(err is not None for _, err in decoded):
+            # a file the probe took and the entropy decoder refused goes to PIL, which may raise as
+            # it always did; the batch is packed again with it as an array
+            self.jpeg.stats["device"] -= sum(err is None for _, err in decoded)
+            for k, (_, err) in zip(enc, decoded):
+                if err is not None:
+                    items[k] = as_array(items[k].data)
+            return self.pack(slot, items)
+        descs = (N.JpegImage * m)()
+        for j, (k, (image, _)) in enumerate(zip(enc, decoded)):
+            image.coef_offset, image.dst_offset, image.ws_offset = coef[j], src[k], ws[j]
+            descs[j] = image
+        hn[jdesc_off:jdesc_off + C_SIZEOF_JPEG_IMAGE * m] = np.frombuffer(descs, np.uint8)
+        for k in plain:
+            a = items[k]
+            hn[src[k]:src[k] + a.nbytes] = a.reshape(-1) if a.flags.c_contiguous else np.ascontiguousarray(a).reshape(-1)
+        shapes = [(a.height, a.width) if isinstance(a, Encoded) else a.shape[:2] for a in items]
+        desc = np.zeros(n, dtype=[("off", "<i8"), ("h", "<i4"), ("w", "<i4")])
+        desc["off"] = src
+        desc["h"] = [h for h, _ in shapes]
+        desc["w"] = [w for _, w in shapes]
+        hn[desc_off:ratio_off] = desc.view(np.uint8)
+        ratios = np.ones(B, np.float32)
+        ratios[:n] = [min(th / h, tw / w) for h, w in shapes]
+        hn[ratio_off:ratio_off + 4 * B] = ratios.view(np.uint8)
+        return n, desc_off, ratio_off, total, (m, jdesc_off)
 
     def launch(self, slot: _Slot, packed_at: tuple, threshold: float) -> _Slot:
         """Device half of a batch, asynchronous: H2D, letterbox, forward, NMS, pack, D2H, event."""
         B, A, (th, tw) = self.batch, self.anchors, self.size
-        n, desc_off, ratio_off, total = packed_at
+        n, desc_off, ratio_off, total, encoded = packed_at
         cfg = self.processor.config
         caller = torch.cuda.current_stream(self.device)
         with torch.cuda.stream(self.copy):
@@ -163,6 +257,9 @@ class Pipeline:
             if not self.inflight:
                 self.main.wait_stream(caller)  # weights the caller's stream was still writing
             self.main.wait_event(slot.h2d_done)
+            if encoded is not None:  # coefficients -> RGB, where the letterbox descriptors point
+                m, jdesc_off = encoded
+                render_batch(pool, pool + jdesc_off, m, pool, pool, self.main.cuda_stream)
             # only the n new images: the other input slots keep their stale contents, n_valid drops them
             N.check(self.lib.yxh_letterbox_batch(pool, pool + desc_off, n, th, tw, N.LB_U8_NHWC,
                                                  self.input.data_ptr(), self.main.cuda_stream), "letterbox")
@@ -207,13 +304,24 @@ class Pipeline:
             self.inflight.popleft().done.synchronize()
 
     # ------------------------------------------------------------------ the stream
+    def prepare(self, im):
+        """One input -> what ``pack`` takes: an ``Encoded`` for a path or encoded bytes the device
+        JPEG decoder accepts (three components: ``as_array`` hands a grayscale file on as 2-D, which
+        the reference rejects), else ``as_array``'s array."""
+        if isinstance(im, (str, os.PathLike) + ENCODED_TYPES):
+            if self.jpeg.on:
+                data = self.jpeg.read(im)
+                return self.jpeg.accept(data) or as_array(data)
+            self.jpeg.accept(b"")  # counted: handed to PIL, the device path is off
+        return as_array(im)
+
     def run(self, inputs: Iterable, threshold: float) -> Iterator[Detections]:
         it = iter(inputs)
         exhausted = False
         try:
             while True:
                 while not exhausted and len(self.inflight) < 2:
-                    chunk = [as_array(im) for im in islice(it, self.batch)]
+                    chunk = [self.prepare(im) for im in islice(it, self.batch)]
                     exhausted = len(chunk) < self.batch
                     if chunk:
                         self.submit(chunk, threshold)
