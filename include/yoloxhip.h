@@ -634,6 +634,20 @@ int yxh_bn_act_bwd(int32_t dtype, int32_t batch, const yxh_src* y, const yxh_src
                    const float* gamma, int32_t act, float* dgamma, float* dbeta, void* dx, void* workspace,
                    size_t workspace_bytes, void* stream);
 
+/*
+ * A BatchNorm2d in eval mode inside a training step (freeze_module, utils/model_utils.py:129-154).
+ * yxh_bn_frozen_stats: stats[4][C] = mean, invstd, gamma*invstd, beta - mean*gamma*invstd from the
+ *   RUNNING statistics (the layout and the scale / shift operation order of yxh_bn_stats; gamma /
+ *   beta may be NULL: 1 / 0).  Nothing is reduced and nothing updated; yxh_bn_act_fwd applies it.
+ * yxh_bn_frozen_act_bwd: dx = dout * act'(y*scale + shift) * scale, elementwise: y a `dtype` view,
+ *   dout an fp32 view, dx dense `dtype` [batch*h*w][C].  Any channel count and any element-aligned
+ *   view: 16-byte accesses where a whole chunk is 16-byte aligned, element by element elsewhere.
+ */
+int yxh_bn_frozen_stats(const float* gamma, const float* beta, const float* running_mean,
+                        const float* running_var, float eps, int32_t channels, float* stats, void* stream);
+int yxh_bn_frozen_act_bwd(int32_t dtype, int32_t batch, const yxh_src* y, const yxh_src* dout, const float* stats,
+                          int32_t act, void* dx, void* stream);
+
 /* out[c] = sum over pixels of x[c] (bias gradients of the head's pred convs). */
 int yxh_channel_sum(int32_t dtype, int32_t batch, const yxh_src* x, float* out, void* workspace,
                     size_t workspace_bytes, void* stream);

@@ -83,6 +83,10 @@ int bn_act_fwd_launch(int dt, int B, const yxh_src* y, const float* stats, int a
                       const yxh_src* out, hipStream_t st);
 int bn_act_bwd_launch(int dt, int B, const yxh_src* y, const yxh_src* dout, const float* stats, const float* gamma,
                       int act, float* dgamma, float* dbeta, void* dx, void* ws, size_t ws_bytes, hipStream_t st);
+int bn_frozen_stats_launch(const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps,
+                           int C, float* stats, hipStream_t st);
+int bn_frozen_act_bwd_launch(int dt, int B, const yxh_src* y, const yxh_src* dout, const float* stats, int act,
+                             void* dx, hipStream_t st);
 int channel_sum_launch(int dt, int B, const yxh_src* x, float* out, void* ws, size_t ws_bytes, hipStream_t st);
 int conv_wgrad_launch(const yxh_wgrad_desc* d, hipStream_t st);
 int pack_dgrad_launch(const float* w, int cout, int cin, int kh, int kw, int c_begin, int c_count, int cout_pad, int dt,
@@ -339,6 +343,16 @@ int yxh_bn_act_bwd(int32_t dtype, int32_t batch, const yxh_src* y, const yxh_src
                    size_t workspace_bytes, void* stream) {
     return bn_act_bwd_launch(dtype, batch, y, dout, stats, gamma, act, dgamma, dbeta, dx, workspace, workspace_bytes,
                              (hipStream_t)stream);
+}
+
+int yxh_bn_frozen_stats(const float* gamma, const float* beta, const float* running_mean, const float* running_var,
+                        float eps, int32_t channels, float* stats, void* stream) {
+    return bn_frozen_stats_launch(gamma, beta, running_mean, running_var, eps, channels, stats, (hipStream_t)stream);
+}
+
+int yxh_bn_frozen_act_bwd(int32_t dtype, int32_t batch, const yxh_src* y, const yxh_src* dout, const float* stats,
+                          int32_t act, void* dx, void* stream) {
+    return bn_frozen_act_bwd_launch(dtype, batch, y, dout, stats, act, dx, (hipStream_t)stream);
 }
 
 int yxh_channel_sum(int32_t dtype, int32_t batch, const yxh_src* x, float* out, void* workspace,

@@ -9,6 +9,10 @@
 //  bn_act_bwd      : act' and BatchNorm backward: dgamma = sum dz*xhat, dbeta = sum dz,
 //                    dx = gamma*invstd*(dz - dbeta/M - xhat*dgamma/M).
 //  channel_sum     : bias gradients of the head's pred convs.
+//  bn_frozen_stats : the same stats[4][C] table from the RUNNING statistics (a BatchNorm in eval mode,
+//                    utils/model_utils.py:129-154 freeze_module): no reduction, nothing updated.
+//  bn_frozen_act_bwd : backward of act(y*scale + shift) with constant scale / shift:
+//                    dx = dout * act'(z) * scale, elementwise.
 #include <cstdlib>
 
 #include "train_common.hpp"
@@ -267,6 +271,70 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply(TView y, TView g, const 
     store_f<T, EPC>(dx + (long long)m * C + c0, o);
 }
 
+// ------------------------------------------------------------------ frozen BatchNorm (eval mode)
+// One thread per channel; the operation order of chan_finalize's STATS branch (invstd from a double
+// sqrt, scale = gamma * invstd, shift = beta - mean * scale in float).
+__global__ __launch_bounds__(256) void bn_frozen_stats_k(const float* gamma, const float* beta, const float* rmean,
+                                                         const float* rvar, float eps, int C, float* stats) {
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= C) return;
+    const float mean = rmean[c];
+    const float invstd = (float)(1.0 / sqrt((double)rvar[c] + (double)eps));
+    const float g = gamma ? gamma[c] : 1.0f, be = beta ? beta[c] : 0.0f;
+    const float scale = g * invstd;
+    stats[c] = mean;
+    stats[C + c] = invstd;
+    stats[2 * C + c] = scale;
+    stats[3 * C + c] = be - mean * scale;
+}
+
+// n <= N live elements at p: one 16-byte access per 16 bytes when the chunk is whole and p is 16-byte
+// aligned, element by element otherwise (the last chunk of a row whose channel count is no multiple of
+// the chunk, rows of a view that do not start on 16 bytes); lanes past n read nothing and hold 0.
+template <typename T, int N>
+__device__ __forceinline__ void load_n(const T* p, int n, float (&o)[N]) {
+    if (n == N && ((uintptr_t)p & 15u) == 0) {
+        load_f<T, N>(p, o);
+    } else {
+#pragma unroll
+        for (int e = 0; e < N; ++e) o[e] = e < n ? to_f32(p[e]) : 0.0f;
+    }
+}
+
+template <typename T, int N>
+__device__ __forceinline__ void store_n(T* p, int n, const float (&o)[N]) {
+    if (n == N && ((uintptr_t)p & 15u) == 0) {
+        store_f<T, N>(p, o);
+    } else {
+#pragma unroll
+        for (int e = 0; e < N; ++e)
+            if (e < n) p[e] = from_f32<T>(o[e]);
+    }
+}
+
+// A lane per (pixel, 16-byte chunk of channels): y (T view), dout (fp32 view), scale / shift rows of the
+// stats table -> dx (T, dense [M][C]).  nch = ceil(C / EPC): the last chunk of a row may be partial.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_frozen_act_bwd_k(TView y, TView g, const float* st, int act, int M, T* dx) {
+    constexpr int EPC = Chunk<T>::N;
+    const int C = y.C, nch = (C + EPC - 1) / EPC;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)M * nch) return;
+    const int m = (int)(idx / nch), c0 = (int)(idx - (long long)m * nch) * EPC;
+    const int n = min(EPC, C - c0);
+    float v[EPC], gv[EPC], sc[EPC], sf[EPC], o[EPC];
+    load_n<T, EPC>((const T*)y.ptr + vofs(y, m) + c0, n, v);
+    load_n<float, EPC>((const float*)g.ptr + vofs(g, m) + c0, n, gv);
+    load_n<float, EPC>(st + 2 * C + c0, n, sc);
+    load_n<float, EPC>(st + 3 * C + c0, n, sf);
+#pragma unroll
+    for (int e = 0; e < EPC; ++e) {
+        const float z = v[e] * sc[e] + sf[e];
+        o[e] = gv[e] * act_grad<sizeof(T) == 4>(z, act) * sc[e];
+    }
+    store_n<T, EPC>(dx + (long long)m * C + c0, n, o);
+}
+
 // ================================================================== host
 namespace {
 
@@ -413,6 +481,48 @@ int bn_act_bwd_launch(int dt, int B, const yxh_src* y, const yxh_src* dout, cons
     else YXH_BNB(float);
 #undef YXH_BNB
     YXH_CHECK_LAUNCH("bn_act_bwd_apply");
+    return YXH_OK;
+}
+
+int bn_frozen_stats_launch(const float* gamma, const float* beta, const float* rmean, const float* rvar, float eps,
+                           int C, float* stats, hipStream_t st) {
+    YXH_CHECK_ARG(C > 0, "bn_frozen_stats: %d channels", C);
+    YXH_CHECK_ARG(rmean && rvar && stats, "bn_frozen_stats: null running statistics / stats");
+    hipLaunchKernelGGL(bn_frozen_stats_k, dim3((C + 255) / 256), dim3(256), 0, st, gamma, beta, rmean, rvar, eps, C,
+                       stats);
+    YXH_CHECK_LAUNCH("bn_frozen_stats");
+    return YXH_OK;
+}
+
+int bn_frozen_act_bwd_launch(int dt, int B, const yxh_src* y, const yxh_src* dout, const float* stats, int act,
+                             void* dx, hipStream_t st) {
+    YXH_CHECK_ARG(dt == YXH_F32 || dt == YXH_BF16 || dt == YXH_F16, "bn_frozen_act_bwd: dtype %d", dt);
+    YXH_CHECK_ARG(y && y->ptr && dout && dout->ptr && stats && dx, "bn_frozen_act_bwd: null view / stats / dx");
+    const int C = y->channels;
+    YXH_CHECK_ARG(B > 0 && C > 0 && y->h > 0 && y->w > 0, "bn_frozen_act_bwd: batch %d, %d channels, %d x %d", B, C,
+                  y->h, y->w);
+    YXH_CHECK_ARG(dout->channels == C && dout->h == y->h && dout->w == y->w, "bn_frozen_act_bwd: dout view shape");
+    YXH_CHECK_ARG(y->upsample == 0 && dout->upsample == 0, "bn_frozen_act_bwd: upsampled views are not read here");
+    // rows inside their pixel stride, images inside their batch stride: every access stays in the views
+    YXH_CHECK_ARG(y->cstride >= C && dout->cstride >= C && y->bstride >= (long long)y->h * y->w * y->cstride &&
+                      dout->bstride >= (long long)y->h * y->w * dout->cstride,
+                  "bn_frozen_act_bwd: view strides smaller than the view");
+    YXH_CHECK_ARG(((uintptr_t)y->ptr % esz(dt)) == 0 && ((uintptr_t)dout->ptr & 3u) == 0 &&
+                      ((uintptr_t)dx % esz(dt)) == 0 && ((uintptr_t)stats & 3u) == 0,
+                  "bn_frozen_act_bwd: pointers not aligned to their element");
+    const long long M = (long long)B * y->h * y->w;
+    YXH_CHECK_ARG(M < (1LL << 31), "too many pixels");
+    const int epc = 16 / esz(dt);
+    const long long total = M * ((C + epc - 1) / epc);
+    YXH_CHECK_ARG((total + 255) / 256 < (1LL << 31), "bn_frozen_act_bwd: grid too large");
+    dim3 grid((unsigned)((total + 255) / 256));
+#define YXH_BNZ(T) \
+    hipLaunchKernelGGL(bn_frozen_act_bwd_k<T>, grid, dim3(256), 0, st, tview(y, C), tview(dout, C), stats, act, (int)M, (T*)dx)
+    if (dt == YXH_BF16) YXH_BNZ(bf16);
+    else if (dt == YXH_F16) YXH_BNZ(f16);
+    else YXH_BNZ(float);
+#undef YXH_BNZ
+    YXH_CHECK_LAUNCH("bn_frozen_act_bwd");
     return YXH_OK;
 }
 

@@ -266,6 +266,8 @@ def lib():
             "yxh_bn_act_fwd": ([i32, i32, C.POINTER(Src), vp, i32, C.POINTER(Src), C.POINTER(Src), vp], C.c_int),
             "yxh_bn_act_bwd": ([i32, i32, C.POINTER(Src), C.POINTER(Src), vp, vp, i32, vp, vp, vp, vp, sz, vp],
                                C.c_int),
+            "yxh_bn_frozen_stats": ([vp, vp, vp, vp, f32, i32, vp, vp], C.c_int),
+            "yxh_bn_frozen_act_bwd": ([i32, i32, C.POINTER(Src), C.POINTER(Src), vp, i32, vp, vp], C.c_int),
             "yxh_channel_sum": ([i32, i32, C.POINTER(Src), vp, vp, sz, vp], C.c_int),
             "yxh_conv_wgrad": ([C.POINTER(WgradDesc), vp], C.c_int),
             "yxh_pack_dgrad_weight": ([vp, i32, i32, i32, i32, i32, i32, i32, i32, vp, vp], C.c_int),
@@ -327,7 +329,8 @@ EXPORTED = ["yxh_abi_version", "yxh_last_error", "yxh_sizeof_op", "yxh_sizeof_co
             "yxh_resize_u8_batch", "yxh_sizeof_resize_image",
             "yxh_rgb_stem_pack", "yxh_rgb_stem_conv", "yxh_rgb_pack",
             "yxh_jpeg_probe", "yxh_jpeg_decode", "yxh_jpeg_workspace_bytes", "yxh_jpeg_render_host",
-            "yxh_jpeg_render_batch", "yxh_sizeof_jpeg_info", "yxh_sizeof_jpeg_image"]
+            "yxh_jpeg_render_batch", "yxh_sizeof_jpeg_info", "yxh_sizeof_jpeg_image",
+            "yxh_bn_frozen_stats", "yxh_bn_frozen_act_bwd"]
 
 
 def check(rc: int, what: str = "") -> None:

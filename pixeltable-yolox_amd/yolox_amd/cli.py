@@ -1,14 +1,19 @@
 """``yolox train`` (reference yolox/cli/train.py:19-143 + cli/utils.py) on the HIP path.
 
     python -m yolox_amd train -c yolox-s -d 8 -b 64 --fp16 [-o] [--resume] [--ckpt FILE] [-e N]
-                              [-D key=value ...]
+                              [--freeze NAME ...] [-D key=value ...]
 
 Same flags and meaning as the reference: ``-c`` a named config (or ``module:Class``),
 ``-d`` processes = GPUs of this machine (one process per GPU, yolox_amd.launch), ``-b`` the
 GLOBAL batch (each rank trains on b / d images), ``--fp16`` mixed precision through
 autocast + GradScaler, ``-D`` config overrides, ``--resume`` continue from ``--ckpt`` or
 ``<output_dir>/<name>/latest_ckpt.pth`` (``-e`` overrides the epoch to start at, 1-based),
-``--ckpt`` alone fine-tune from a checkpoint's matching weights.  Every epoch end writes
+``--ckpt`` alone fine-tune from a checkpoint's matching weights.  ``--freeze NAME [NAME ...]`` (added; also
+``-D freeze=NAME,NAME``) freezes, after the weights are loaded, every parameter and sub-module whose name
+contains NAME (``yolox_amd.utils.freeze_module``: ``requires_grad`` off, BatchNorm in eval mode), e.g.
+``backbone`` (CspDarknet + PAFPN), ``backbone.backbone`` (CspDarknet) or ``head.stems``; the HIP step then
+skips their backward and BatchNorm statistics, the optimizer leaves them alone, and a NAME that matches
+nothing is an error.  Every epoch end writes
 checkpoints there and, with an evaluation dataset (``YoloxConfig.get_eval_dataset``),
 evaluates (yolox_amd.trainer).  ``-D data_dir=/path/to/COCO`` trains on a COCO-layout directory
 (``annotations/<train_ann>``, ``train2017/``; yolox_amd.data.CocoDataset streamed through an HBM
@@ -81,6 +86,8 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("-D", type=str, metavar="OPT=VALUE", action="append")
     p.add_argument("--max-iter", dest="max_iter", type=int, default=None, help="stop after this many iterations")
     p.add_argument("--dataset-size", dest="dataset_size", type=int, default=118287)
+    p.add_argument("--freeze", type=str, nargs="+", default=None, metavar="NAME",
+                   help="freeze parameters / sub-modules whose name contains NAME (e.g. backbone, head.stems)")
     return p
 
 
@@ -107,6 +114,8 @@ def main(argv: list) -> None:
     check_args(args)
     config = resolve_config(args.config)
     config.update(parse_model_config_opts(args.D))
+    if args.freeze:
+        config.update({"freeze": tuple(args.freeze)})
     config.validate()
     if not args.name:
         args.name = config.name
@@ -122,5 +131,5 @@ def cli(argv=None) -> None:
     argv = sys.argv[1:] if argv is None else argv
     if not argv or argv[0] != "train":
         sys.exit("usage: python -m yolox_amd train -c <config> [-d N] [-b B] [--fp16] [--resume] [--ckpt FILE] "
-                 "[-e N] [-D k=v ...]")
+                 "[-e N] [--freeze NAME ...] [-D k=v ...]")
     main(argv[1:])

@@ -68,6 +68,8 @@ class YoloxConfig:
     print_interval: int = 10
     eval_interval: int = 10
     save_history_ckpt: bool = True
+    # fine-tuning: names for yolox_amd.utils.freeze_module(model, name), e.g. ("backbone",) or ("head.stems",)
+    freeze: tuple = ()
     # testing
     test_size: tuple[int, int] = (640, 640)
     test_conf: float = 0.01
@@ -88,6 +90,10 @@ class YoloxConfig:
             if not hasattr(self, k) or k == "model":
                 raise AttributeError(f"Unknown model configuration option: {k}")
             cur = getattr(self, k)
+            if k == "freeze":  # names, not numbers: "a,b", ("a", "b") or ["a"]; empty entries dropped
+                items = v if isinstance(v, (list, tuple)) else str(v).strip("[]()").split(",")
+                setattr(self, k, tuple(t for t in (str(i).strip().strip("'\"") for i in items) if t))
+                continue
             if isinstance(cur, (list, tuple)):
                 items = [t.strip() for t in str(v).strip("[]()").split(",")]
                 if cur:

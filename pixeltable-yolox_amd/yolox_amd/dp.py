@@ -214,10 +214,10 @@ class DistributedDataParallel(nn.Module):
         out = self.module(*args, **kwargs)
         if self.module.training:
             g = self.module._train_graph
-            if self._reducer is None or self._graph_id != id(g):
-                gb = g.grads
+            gb = g.grads  # the trainable parameters only; rebuilt (a new serial) when the freeze pattern changes
+            if self._reducer is None or self._graph_id != (id(g), gb.serial):
                 self._reducer = GradReducer(gb.flat, gb.params, gb.offsets, self.bucket_cap_mb, self.process_group)
-                self._graph_id = id(g)
+                self._graph_id = (id(g), gb.serial)
             red = self._reducer
             red.reset()
             g.on_param_ready = red.ready

@@ -14,6 +14,12 @@ scaler.update()`` + EMA): the GradScaler's scale / growth tracker tensors are us
 place, the inf/NaN check, the in-place unscale, the skipped-or-taken SGD update, the EMA
 update and ``_amp_update_scale_`` all run on the device in three launches, with no host
 synchronisation (torch's GradScaler.step reads found_inf with ``.item()``).
+
+Frozen parameters (``requires_grad`` false, ``yolox_amd.utils.freeze_module``): torch's SGD skips a
+parameter whose ``.grad`` is None -- no weight decay, no momentum, no update.  Here such a parameter is
+an EMA-only segment of the table (``param == NULL``, ``src`` = the parameter, the form the BN buffers
+already use): the EMA copy keeps following it, nothing else touches it, and the inf scan (which skips
+``param == NULL`` segments) covers the trainable gradients only.
 """
 from __future__ import annotations
 
@@ -56,7 +62,8 @@ class FusedStep:
         self.bufs = {id(p): self.flat_buf[offs[id(p)]:offs[id(p)] + p.numel()].view_as(p) for p in params}
         held = [p for p in params if "momentum_buffer" in optimizer.state.get(p, {})
                 and optimizer.state[p]["momentum_buffer"] is not None]
-        if held and len(held) != len(params):
+        # a frozen parameter has no optimizer state, as under torch's SGD (grad None: skipped); every other has it or none
+        if held and {id(p) for p in params if p.requires_grad} - {id(p) for p in held}:
             raise ValueError("FusedStep: momentum buffers exist for some parameters only")
         for p in held:  # resume: continue from the optimizer's buffers, which become the views
             self.bufs[id(p)].copy_(optimizer.state[p]["momentum_buffer"])
@@ -84,14 +91,20 @@ class FusedStep:
         self.found_inf = torch.zeros(1, dtype=torch.float32, device=self.device)
 
     def _table(self):
-        grads = [p.grad for p in self.params]
-        if any(g is None for g in grads):
+        frozen = tuple(not p.requires_grad for p in self.params)
+        grads = [None if f else p.grad for p, f in zip(self.params, frozen)]
+        if any(g is None and not f for g, f in zip(grads, frozen)):
             raise RuntimeError("FusedStep: every parameter needs a gradient (the HIP reverse pass writes all)")
-        key = tuple(g.data_ptr() for g in grads)
+        key = (tuple(g.data_ptr() if g is not None else 0 for g in grads), frozen)
         if key == self._key:
             return
         segs, chunks = [], []
         for p, g in zip(self.params, grads):
+            if g is None:  # frozen: torch SGD's skip of grad None; its EMA copy still follows it
+                e = self.ema_of.get(id(p))
+                if e is not None:
+                    segs.append(N.OptSeg(None, None, None, e.data_ptr(), p.data_ptr(), e.numel(), 0.0, 0))
+                continue
             if g.dtype != torch.float32 or not g.is_contiguous():
                 raise ValueError("FusedStep: fp32 contiguous gradients only")
             gi = self.group[id(p)]
@@ -104,6 +117,8 @@ class FusedStep:
         for i, s in enumerate(segs):
             for c in range((s.n + self.chunk - 1) // self.chunk):
                 chunks += [i, c]
+        if not segs:
+            raise ValueError("FusedStep: nothing to step (every parameter is frozen and there is no EMA)")
         raw = (N.OptSeg * len(segs))(*segs)
         self.d_segs = torch.frombuffer(bytearray(raw), dtype=torch.uint8).to(self.device)
         self.d_chunks = torch.tensor(chunks, dtype=torch.int32).to(self.device)
@@ -122,9 +137,7 @@ class FusedStep:
             N.check(self.lib.yxh_amp_found_inf(self.d_segs.data_ptr(), self.d_chunks.data_ptr(), self.nchunks,
                                                self.found_inf.data_ptr(), st), "amp_found_inf")
             if self.first:  # zero buffers: b*m + g == g exactly, the first step needs no flag
-                for p in self.params:
-                    self.opt.state[p]["momentum_buffer"] = self.bufs[id(p)]
-                self.first = False
+                self._publish_buffers()
         hp = N.OptHparams()
         for gi, g in enumerate(self.opt.param_groups):
             hp.lr[gi] = float(g["lr"])
@@ -145,19 +158,25 @@ class FusedStep:
                 float(scaler._growth_factor), float(scaler._backoff_factor), int(scaler._growth_interval),
                 N.stream_ptr(self.device)), "amp_update_scale")
             torch.autograd.graph.increment_version([scaler._scale, scaler._growth_tracker] +
-                                                   [p.grad for p in self.params])
+                                                   [p.grad for p in self.params if p.requires_grad])
         if self.first:
-            for p in self.params:
-                self.opt.state[p]["momentum_buffer"] = self.bufs[id(p)]
-            self.first = False
+            self._publish_buffers()
         # in-place writes behind torch's back: bump versions (eager plans) and the modules'
         # weights epochs (captured plans) so eval plans repack
-        torch.autograd.graph.increment_version(self.params)
+        torch.autograd.graph.increment_version([p for p in self.params if p.requires_grad])
         for m in (getattr(self.model, "module", self.model), getattr(self.ema, "ema", None)):
             if hasattr(m, "weights_changed"):
                 m.weights_changed()
         if self.ema is not None:
             torch.autograd.graph.increment_version(list(self.ema.ema.parameters()))
+
+    def _publish_buffers(self) -> None:
+        """After the first step: the optimizer's momentum buffers are the views of the flat buffer -- for the
+        parameters that were stepped; a frozen one keeps an empty state, as torch's SGD leaves it."""
+        for p in self.params:
+            if p.requires_grad:
+                self.opt.state[p]["momentum_buffer"] = self.bufs[id(p)]
+        self.first = False
 
     def _check_scaler(self, scaler) -> None:
         from torch.amp.grad_scaler import OptState

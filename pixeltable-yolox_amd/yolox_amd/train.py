@@ -21,6 +21,13 @@ closures; ``backward`` replays it in reverse:
 * DWConv (yolox_nano): the depthwise conv forward on yxh_conv2d (groups = channels), its
   gradients on yxh_dw_wgrad / yxh_dw_dgrad.
 
+Frozen modules (``yolox_amd.utils.freeze_module``; DESIGN.md "Frozen modules"): the step reads
+``requires_grad`` of every parameter and ``.training`` of every BatchNorm.  A BatchNorm in eval mode
+normalises with its running statistics and leaves them alone; a BaseConv that is frozen and has no
+trainable layer upstream runs as ONE conv launch with the BatchNorm folded into its weights (the eval
+path's form) and records nothing for the reverse pass; a frozen BatchNorm that still passes a gradient
+goes back through yxh_bn_frozen_act_bwd; weight / data gradients run only where somebody needs them.
+
 Parameter gradients land in one flat fp32 buffer (``GradBuffer``) whose slices become
 ``param.grad``; a data-parallel reducer (yolox_amd.dp) can all-reduce it in buckets as
 the reverse pass completes them (``on_param_ready``).
@@ -92,11 +99,16 @@ def dense_src(t: torch.Tensor, up: int = 0) -> N.Src:
 
 
 class GradBuffer:
-    """One flat fp32 buffer holding every parameter gradient, parameters in reverse
-    registration order (roughly the order the reverse pass finishes them)."""
+    """One flat fp32 buffer holding the gradient of every parameter that requires one, parameters in
+    reverse registration order (roughly the order the reverse pass finishes them).  A parameter with
+    ``requires_grad`` false is not held: its ``.grad`` stays None, as in torch."""
+
+    _serial = 0
 
     def __init__(self, params: Sequence[nn.Parameter], device):
-        self.params = list(params)[::-1]
+        GradBuffer._serial += 1
+        self.serial = GradBuffer._serial  # a rebuilt buffer (the freeze pattern changed) is a new one to yolox_amd.dp
+        self.params = [p for p in params if p.requires_grad][::-1]
         self.offsets = {}
         off = 0
         for p in self.params:
@@ -109,6 +121,9 @@ class GradBuffer:
 
     def of(self, p: nn.Parameter) -> torch.Tensor:
         return self.views[id(p)]
+
+    def holds(self, p: Optional[nn.Parameter]) -> bool:
+        return p is not None and id(p) in self.views
 
     def begin(self) -> Optional[torch.Tensor]:
         """Zero the buffer for a new reverse pass; returns what param.grad held if the
@@ -183,7 +198,14 @@ class TrainGraph:
         self.device = model.device
         self.lib = N.lib()
         self.esize = torch.empty((), dtype=dtype).element_size()
-        self.grads = GradBuffer(model.parameters(), self.device)
+        self._params = list(model.parameters())
+        self._bns = [m for m in model.modules() if isinstance(m, nn.modules.batchnorm._BatchNorm)]
+        self._freeze_sig = self.freeze_signature()
+        self._freeze_ok = False  # the pattern of _freeze_sig passed _sync_freeze's refusal check
+        self.grads = GradBuffer(self._params, self.device)
+        # dgamma / dbeta of a train-mode BatchNorm whose gamma / beta are frozen: written, never read
+        self._discard = torch.empty(2, MAX_CHANNELS, dtype=torch.float32, device=self.device)
+        self._fold_w: dict = {}  # BN-folded weights of the frozen prefix (packed every step, one launch each)
         self.ws = torch.empty(int(self.lib.yxh_reduce_workspace_bytes(MAX_CHANNELS)), dtype=torch.uint8,
                               device=self.device)
         self.zero_bias = torch.zeros(MAX_CHANNELS, dtype=torch.float32, device=self.device)
@@ -234,6 +256,54 @@ class TrainGraph:
         if self.on_param_ready is not None:
             for p in params:
                 self.on_param_ready(p)
+
+    # ------------------------------------------------------------ frozen modules
+    def freeze_signature(self) -> tuple:
+        """What the step reads of the freeze pattern: requires_grad per parameter, .training per BatchNorm."""
+        return (tuple(p.requires_grad for p in self._params), tuple(m.training for m in self._bns))
+
+    def _sync_freeze(self) -> None:
+        """Before any device work of a forward: refuse what is not built, and hold exactly the
+        trainable parameters' gradients (a changed pattern rebuilds the gradient buffer)."""
+        sig = self.freeze_signature()
+        if sig == self._freeze_sig and self._freeze_ok:
+            return
+        for name, m in self.model.named_modules():
+            if isinstance(m, nn.modules.batchnorm._BatchNorm) and not m.training and (
+                    m.weight.requires_grad or m.bias.requires_grad):
+                raise NotImplementedError(
+                    f"BatchNorm {name!r} is in eval mode but its weight / bias require grad: gradients of gamma / "
+                    "beta over frozen statistics are not built (freeze them too, or put the module in train mode)")
+        if sig != self._freeze_sig:
+            # gradients still published from the old buffer would be added into its views, beside the new flat
+            # buffer a reducer averages: drop them (the caller zeroes gradients before a step anyway)
+            old = self.grads
+            for p in old.params:
+                if p.grad is not None and p.grad.data_ptr() == old.of(p).data_ptr():
+                    p.grad = None
+            self.grads = GradBuffer(self._params, self.device)
+            self._freeze_sig = sig
+        self._freeze_ok = True
+
+    def _folded_weight(self, conv: nn.Conv2d, bn: nn.BatchNorm2d, cin_pad: int):
+        """conv.weight with the eval-mode BatchNorm folded in -> [cout][kh][kw][cin_pad] compute dtype + the folded
+        fp32 bias: what the eval plans pack (yxh_fold_bn_pack with its BN arguments)."""
+        kh, kw = conv.kernel_size
+        w = self._fold_w.get(id(conv))
+        if w is None:
+            w = (torch.empty(conv.out_channels * kh * kw * cin_pad, dtype=self.dtype, device=self.device),
+                 torch.empty(conv.out_channels, dtype=torch.float32, device=self.device))
+            self._fold_w[id(conv)] = w
+        wt = conv.weight.detach()
+        if wt.dtype != torch.float32:
+            raise ValueError("training keeps fp32 master weights; the compute dtype comes from autocast")
+        b = conv.bias.detach() if conv.bias is not None else None
+        self._chk(self.lib.yxh_fold_bn_pack(
+            wt.data_ptr(), b.data_ptr() if b is not None else None, bn.weight.detach().data_ptr(),
+            bn.bias.detach().data_ptr(), bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps),
+            conv.out_channels, conv.in_channels // conv.groups, kh, kw, cin_pad, self.dcode, w[0].data_ptr(),
+            w[1].data_ptr(), self.stream), "fold + pack weights")
+        return w
 
     def _fwd_weight(self, conv: nn.Conv2d, cin_pad: int):
         """conv.weight -> [cout][kh][kw][cin_pad] compute dtype (+ fp32 bias)."""
@@ -292,7 +362,8 @@ class TrainGraph:
 
     def _conv(self, srcs: list, cin: int, cout: int, k: int, stride: int, pad: int, weight: int, bias: int,
               dst: int, dst_f32: bool, dst_cs: int, dst_bs: int, in_h: int, in_w: int, out_h: int, out_w: int,
-              batch: int, accumulate: bool = False, groups: int = 1) -> None:
+              batch: int, accumulate: bool = False, groups: int = 1, act: int = N.ACT_NONE,
+              residual: Optional[Act] = None) -> None:
         d = N.ConvDesc()
         d.dtype, d.batch = self.dcode, batch
         d.in_h, d.in_w, d.out_h, d.out_w = in_h, in_w, out_h, out_w
@@ -304,10 +375,16 @@ class TrainGraph:
         d.dst = dst
         d.dst_dtype = N.F32 if dst_f32 else self.dcode
         d.dst_cstride, d.dst_bstride = dst_cs, dst_bs
-        d.act = N.ACT_NONE
+        d.act = act
+        if residual is not None:
+            d.residual = residual.t.data_ptr() + residual.coff * residual.t.element_size()
+            d.res_cstride = residual.t.shape[3]
+            d.res_bstride = residual.h * residual.w * residual.t.shape[3]
         d.flags = N.CONV_ACCUMULATE if accumulate else 0
         key = ("conv", self.dcode, batch, in_h, in_w, out_h, out_w, cin, cout, k, stride, pad, int(dst_f32),
                dst_cs, d.flags) + tuple(_src_key(q) for q in srcs)
+        if act != N.ACT_NONE or residual is not None:  # the frozen prefix's folded convs: shapes of their own
+            key += (("fused", act, residual.t.shape[3] if residual is not None else 0),)
         # depthwise convs have one kernel (dwconv): nothing to tune
         d.tile = 0 if groups != 1 else self._tile(key, d, self.lib.yxh_conv2d, "dst",
                                                   batch * dst_bs * (4 if dst_f32 else self.esize),
@@ -503,27 +580,49 @@ class TrainGraph:
             # yolox_tiny widths all meet this
             raise NotImplementedError(f"depthwise conv training needs channels % {16 // self.esize} == 0 "
                                       f"(16-byte gradient rows), got {cout}")
-        w, _ = self._fwd_weight(conv, 1 if dw else cin)
+        gb = self.grads
+        w_train, g_train, b_train = gb.holds(conv.weight), gb.holds(bn.weight), gb.holds(bn.bias)
+        frozen_bn = not bn.training  # eval mode: the running statistics, read only
+        in_needs = any(a.needs_grad for a, _ in inputs)
+        # the output needs a gradient when this layer trains something or anything upstream does
+        needs = w_train or g_train or b_train or in_needs or (residual is not None and residual.needs_grad)
+        act = N.ACT_CODE[getattr(m, "act_name", "silu")]
         srcs = [a.src(up) for a, up in inputs]
+        if out is None:
+            out = Act(torch.empty(B, oh, ow, cout, dtype=self.dtype, device=self.device), 0, cout)
+        out.needs_grad = needs
+        if frozen_bn and not needs:
+            # the frozen prefix: BN folded into the weights, conv + bias + act (+ residual) in one launch straight
+            # into the output view; no raw output, nothing on the tape
+            wf, bf = self._folded_weight(conv, bn, 1 if dw else cin)
+            self._conv(srcs, cin, cout, k, s, p, wf.data_ptr(), bf.data_ptr(),
+                       out.t.data_ptr() + out.coff * self.esize, False, out.t.shape[3], oh * ow * out.t.shape[3],
+                       in_h, in_w, oh, ow, B, groups=conv.groups, act=act, residual=residual)
+            return out
+        w, _ = self._fwd_weight(conv, 1 if dw else cin)
         y = torch.empty(B, oh, ow, cout, dtype=self.dtype, device=self.device)
         self._conv(srcs, cin, cout, k, s, p, w.data_ptr(), self.zero_bias.data_ptr(), y.data_ptr(), False, cout,
                    oh * ow * cout, in_h, in_w, oh, ow, B, groups=conv.groups)
         stats = torch.empty(4, cout, dtype=torch.float32, device=self.device)
         ys = dense_src(y)
-        self._chk(self.lib.yxh_bn_stats(
-            self.dcode, B, C.byref(ys), bn.weight.detach().data_ptr(), bn.bias.detach().data_ptr(),
-            bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps), float(bn.momentum),
-            stats.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.stream), "bn stats")
-        self._bn_counters.append(bn.num_batches_tracked)  # += 1 for all BNs in one launch (forward end)
-        if out is None:
-            out = Act(torch.empty(B, oh, ow, cout, dtype=self.dtype, device=self.device), 0, cout)
+        if frozen_bn:  # the same table from the running statistics; nothing updated
+            self._chk(self.lib.yxh_bn_frozen_stats(
+                bn.weight.detach().data_ptr(), bn.bias.detach().data_ptr(), bn.running_mean.data_ptr(),
+                bn.running_var.data_ptr(), float(bn.eps), cout, stats.data_ptr(), self.stream), "bn frozen stats")
+        else:
+            self._chk(self.lib.yxh_bn_stats(
+                self.dcode, B, C.byref(ys), bn.weight.detach().data_ptr(), bn.bias.detach().data_ptr(),
+                bn.running_mean.data_ptr(), bn.running_var.data_ptr(), float(bn.eps), float(bn.momentum),
+                stats.data_ptr(), self.ws.data_ptr(), self.ws.numel(), self.stream), "bn stats")
+            self._bn_counters.append(bn.num_batches_tracked)  # += 1 for all BNs in one launch (forward end)
         os_ = out.src()
         rs = residual.src() if residual is not None else None
-        act = N.ACT_CODE[getattr(m, "act_name", "silu")]
         self._chk(self.lib.yxh_bn_act_fwd(self.dcode, B, C.byref(ys), stats.data_ptr(), act,
                                           C.byref(rs) if rs is not None else None, C.byref(os_), self.stream),
                   "bn act fwd")
         cin_store = cin_store or cin
+        if not needs:  # train-mode statistics over frozen parameters with nothing trainable upstream
+            return out
 
         def backward():
             if out.grad is None:  # output unused by the loss
@@ -531,20 +630,26 @@ class TrainGraph:
             assert y.data_ptr() == ys.ptr  # the closure holds y: ys is a raw pointer into it
             dy = torch.empty(B, oh, ow, cout, dtype=self.dtype, device=self.device)
             go = dense_src(out.grad)
-            gb = self.grads
-            self._chk(self.lib.yxh_bn_act_bwd(
-                self.dcode, B, C.byref(ys), C.byref(go), stats.data_ptr(), bn.weight.detach().data_ptr(), act,
-                gb.of(bn.weight).data_ptr(), gb.of(bn.bias).data_ptr(), dy.data_ptr(), self.ws.data_ptr(),
-                self.ws.numel(), self.stream), "bn act bwd")
-            self._ready(bn.weight, bn.bias)
+            if frozen_bn:  # constant scale / shift: dy = dout * act'(z) * scale, no reduction
+                if w_train or in_needs:
+                    self._chk(self.lib.yxh_bn_frozen_act_bwd(self.dcode, B, C.byref(ys), C.byref(go), stats.data_ptr(),
+                                                             act, dy.data_ptr(), self.stream), "bn frozen act bwd")
+            else:
+                self._chk(self.lib.yxh_bn_act_bwd(
+                    self.dcode, B, C.byref(ys), C.byref(go), stats.data_ptr(), bn.weight.detach().data_ptr(), act,
+                    (gb.of(bn.weight) if g_train else self._discard[0]).data_ptr(),
+                    (gb.of(bn.bias) if b_train else self._discard[1]).data_ptr(), dy.data_ptr(), self.ws.data_ptr(),
+                    self.ws.numel(), self.stream), "bn act bwd")
+                self._ready(*[q for q, held in ((bn.weight, g_train), (bn.bias, b_train)) if held])
             if residual is not None and residual.needs_grad:
                 if residual.grad is None:  # first writer: take over out.grad (consumed above)
                     residual.grad = out.grad
                 else:
                     residual.grad.add_(out.grad)
             if dw:  # depthwise gradients: yxh_dw_wgrad (side stream) and yxh_dw_dgrad
-                self._side_wgrad(lambda: self._dw_wgrad(srcs[0], dense_src(dy), cout, s, oh, ow, B,
-                                                        gb.of(conv.weight)), dy, conv.weight)
+                if w_train:
+                    self._side_wgrad(lambda: self._dw_wgrad(srcs[0], dense_src(dy), cout, s, oh, ow, B,
+                                                            gb.of(conv.weight)), dy, conv.weight)
                 a = inputs[0][0]
                 if a.needs_grad:
                     g, acc = a.grad_target()
@@ -552,8 +657,9 @@ class TrainGraph:
                                                     in_h, in_w, g.data_ptr(), a.ch, in_h * in_w * a.ch, int(acc),
                                                     self.stream), "dw dgrad")
                 return
-            self._side_wgrad(lambda: self._wgrad(srcs, cin, cin_store, cout, k, s, p, dense_src(dy), gb.of(conv.weight),
-                                                 in_h, in_w, oh, ow, B), dy, conv.weight)
+            if w_train:
+                self._side_wgrad(lambda: self._wgrad(srcs, cin, cin_store, cout, k, s, p, dense_src(dy),
+                                                     gb.of(conv.weight), in_h, in_w, oh, ow, B), dy, conv.weight)
             off, ins = 0, []
             for a, up in inputs:
                 ins.append((a, up, off))
@@ -586,7 +692,9 @@ class TrainGraph:
         x = self.base_conv(m.conv1, inputs, out=Act(cat, 0, c))
         self._chk(self.lib.yxh_spp_maxpool(cat.data_ptr(), self.dcode, B, h, w, c, 4 * c, h * w * 4 * c,
                                            self.stream), "spp")
-        cat_act = Act(cat, 0, 4 * c)
+        cat_act = Act(cat, 0, 4 * c, needs_grad=x.needs_grad)
+        if not x.needs_grad:  # frozen prefix: pooling a map nobody differentiates
+            return self.base_conv(m.conv2, [(cat_act, 0)])
 
         def backward():
             if cat_act.grad is None:
@@ -698,6 +806,8 @@ class TrainGraph:
         self.assign = {"fg_mask": fg, "matched_gt_inds": matched, "pred_ious": piou, "num_fg": num_fg}
         self.outputs = preds
 
+        gb = self.grads
+
         def backward():
             g_ro = torch.empty(B, A, 8, dtype=self.dtype, device=self.device)
             g_cls = torch.empty(B, A, nc, dtype=self.dtype, device=self.device)
@@ -713,7 +823,6 @@ class TrainGraph:
                 g_pad = torch.zeros(B, A, ncp, dtype=self.dtype, device=self.device)
                 g_pad[..., :nc].copy_(g_cls)
                 g_cls = g_pad
-            gb = self.grads
             for k, r, c, w_ro, a0, h, w in reversed(levels):
                 for g_all, ch, feat, wmat, convs in (
                         (g_ro, 8, r, w_ro, (head.reg_preds[k], head.obj_preds[k])),
@@ -723,19 +832,27 @@ class TrainGraph:
                     dys.ptr = g_all.data_ptr() + a0 * ch * self.esize
                     dys.channels, dys.cstride, dys.bstride = ch, ch, A * ch
                     dys.h, dys.w, dys.upsample = h, w, 0
-                    # weight gradient (stacked rows) and bias sums
-                    dw = torch.zeros(cout, feat.ch, dtype=torch.float32, device=self.device)
-                    self._wgrad([feat.src()], feat.ch, feat.ch, cout, 1, 1, 0, dys, dw, h, w, h, w, B)
-                    bsum = torch.empty(ch, dtype=torch.float32, device=self.device)
-                    self._chk(self.lib.yxh_channel_sum(self.dcode, B, C.byref(dys), bsum.data_ptr(),
-                                                       self.ws.data_ptr(), self.ws.numel(), self.stream), "bias sum")
+                    # weight gradient (stacked rows) and bias sums, where a pred conv's weight / bias train
+                    dw = bsum = None
+                    if any(gb.holds(cv.weight) for cv in convs):
+                        dw = torch.zeros(cout, feat.ch, dtype=torch.float32, device=self.device)
+                        self._wgrad([feat.src()], feat.ch, feat.ch, cout, 1, 1, 0, dys, dw, h, w, h, w, B)
+                    if any(gb.holds(cv.bias) for cv in convs):
+                        bsum = torch.empty(ch, dtype=torch.float32, device=self.device)
+                        self._chk(self.lib.yxh_channel_sum(self.dcode, B, C.byref(dys), bsum.data_ptr(),
+                                                           self.ws.data_ptr(), self.ws.numel(), self.stream),
+                                  "bias sum")
                     row = 0
                     for cv in convs:
                         n = cv.out_channels
-                        gb.of(cv.weight).copy_(dw[row:row + n].view_as(cv.weight))
-                        gb.of(cv.bias).copy_(bsum[row:row + n])
+                        if gb.holds(cv.weight):
+                            gb.of(cv.weight).copy_(dw[row:row + n].view_as(cv.weight))
+                        if gb.holds(cv.bias):
+                            gb.of(cv.bias).copy_(bsum[row:row + n])
                         row += n
-                        self._ready(cv.weight, cv.bias)
+                        self._ready(*[q for q in (cv.weight, cv.bias) if gb.holds(q)])
+                    if not feat.needs_grad:  # the whole branch below the preds is frozen
+                        continue
                     # data gradient: 1x1 conv with the transposed pred weights (K padded to `ch`)
                     wt = torch.empty(feat.ch * ch, dtype=self.dtype, device=self.device)
                     wm = wmat.contiguous()
@@ -756,6 +873,7 @@ class TrainGraph:
             raise ValueError(f"expected [B, 3, H, W] images, got {tuple(images.shape)}")
         if images.shape[2] % 32 or images.shape[3] % 32:
             raise ValueError("input size must be multiples of 32")
+        self._sync_freeze()
         images = images.to(self.device)
         if images.dtype not in (torch.float32, torch.bfloat16, torch.float16, torch.uint8):
             images = images.float()
@@ -815,6 +933,11 @@ class CapturedTrainStep:
     all-reduces are issued between segments, overlapping the later segments), and finishes the
     reducer behind the last segment (1/world mean on the compute stream), as the eager backward does.
 
+    The freeze pattern (``requires_grad`` of every parameter, ``.training`` of every BatchNorm) is part
+    of what the capture holds, as ``head.use_l1`` is: it decided which launches exist.  The eager step
+    before the capture must have run with the same pattern, and a call after the pattern changed
+    raises instead of replaying a stale graph (freeze, run an eager step, capture again).
+
     The graph holds the loss kernels the capture launched: like ``head.use_l1``, the box loss type
     (``head.iou_loss.loss_type``, iou or giou) is the one the head had at capture; changing either
     afterwards needs a new capture.
@@ -835,6 +958,10 @@ class CapturedTrainStep:
         self.reducer = getattr(self.on_ready, "__self__", None)
         if g.batch_pack and g._pack_table is None:
             raise RuntimeError("CapturedTrainStep: the repack table is not recorded yet (run an eager step)")
+        if g.freeze_signature() != g._freeze_sig:
+            raise RuntimeError("CapturedTrainStep: the freeze pattern changed since the last eager step; run one "
+                               "eager training step with it first")
+        self.freeze_sig = g._freeze_sig
         self.model, self.g, self.dev = model, g, model.device
         self.images = images.to(model.device).clone()
         self.targets = targets.to(model.device).clone()
@@ -959,6 +1086,9 @@ class CapturedTrainStep:
     def __call__(self, images: torch.Tensor, targets: torch.Tensor) -> dict:
         if images.shape != self.images.shape or targets.shape != self.targets.shape:
             raise ValueError("CapturedTrainStep: batch shape differs from the captured one")
+        if self.g.freeze_signature() != self.freeze_sig:
+            raise RuntimeError("CapturedTrainStep: the freeze pattern (requires_grad / BatchNorm modes) differs from "
+                               "the captured one; capture again after an eager step")
         if images.data_ptr() != self.images.data_ptr():
             self.images.copy_(images, non_blocking=True)
         if targets.data_ptr() != self.targets.data_ptr():
@@ -1021,6 +1151,12 @@ class _BlockOwner:
     def parameters(self):
         return self.block.parameters()
 
+    def modules(self):
+        return self.block.modules()
+
+    def named_modules(self):
+        return self.block.named_modules()
+
     @property
     def device(self) -> torch.device:
         return next(self.block.parameters()).device
@@ -1045,6 +1181,9 @@ class _BlockFn(torch.autograd.Function):
     def backward(ctx, *gouts):
         if ctx.tape is None:
             raise RuntimeError("block backward called twice on one forward (retain_graph is not supported)")
+        if not ctx.tape:  # a wholly frozen block on an input that needs no gradient: nothing was recorded
+            ctx.tape = ctx.keep = None
+            return None, None, None, None
         for a, go in zip(ctx.acts, gouts):
             if go is not None:
                 a.grad = go.permute(0, 2, 3, 1).to(torch.float32).contiguous()
@@ -1073,6 +1212,8 @@ def block_train_forward(block: nn.Module, x: torch.Tensor, dtype: Optional[torch
         block.__dict__["_train_graph_block"] = g
     dev = owner.device
     x = x.to(dev)
+
+    g._sync_freeze()
 
     def run():
         g.tape = []

@@ -204,7 +204,8 @@ class Trainer:
     fused SGD + EMA (+ GradScaler) step, LR update; ``after_iter`` redraws the input size
     every 10 iterations on rank 0 and broadcasts it (:301-306).  Logging is a print every
     ``print_interval`` iterations on rank 0.  ``args.max_iter`` (not in the reference) stops
-    after that many iterations.
+    after that many iterations.  ``config.freeze`` (``--freeze NAME ...``, not in the reference's trainer; its
+    ``freeze_module`` is what users call by hand) freezes the named parts before anything is built on the model.
 
     Epoch ends (:232-237, :347-429): ``after_epoch`` writes ``latest_ckpt.pth`` and, every
     ``eval_interval`` epochs, averages the BN state over the ranks (dp.all_reduce_norm) and
@@ -283,6 +284,8 @@ class Trainer:
         model.to(self.device)
         self.optimizer = self.exp.get_optimizer(self.args.batch_size)
         model = self.resume_train(model)  # sets start_epoch
+        # config.freeze / --freeze: after the weights are in, before EMA, the fused step and DDP see the model
+        self.apply_freeze(model)
         self.no_aug =self.start_epoch >= self.max_epoch - self.exp.no_aug_epochs
         self.train_loader = self.exp.get_data_loader(batch_size=self.args.batch_size,
                                                      is_distributed=self.is_distributed, no_aug=self.no_aug,
@@ -302,6 +305,23 @@ class Trainer:
         dataset = self.exp.get_eval_dataset(testdev=False, legacy=False)
         self.evaluator = None if dataset is None else self.exp.get_evaluator(
             batch_size=self.args.batch_size, is_distributed=self.is_distributed, dataset=dataset)
+
+    def apply_freeze(self, model) -> None:
+        """``freeze_module(model, name)`` for every name of ``config.freeze``: requires_grad off on the matching
+        parameters, eval mode on the matching sub-modules.  Called once, from before_train: the trainer never
+        calls ``model.train()`` afterwards (which would undo the eval half), and evaluate_and_save_model restores
+        every module's own mode.  A name that matches nothing is an error."""
+        from .utils.model_utils import freeze_module, frozen_names
+        m = model.module if hasattr(model, "module") else model
+        for name in getattr(self.exp, "freeze", ()) or ():
+            params, mods = frozen_names(m, name)
+            if not params and not mods:
+                raise ValueError(f"freeze: no parameter or sub-module of the model has {name!r} in its name")
+            freeze_module(m, name)
+        if self.rank == 0 and getattr(self.exp, "freeze", ()):
+            n = sum(1 for p in m.parameters() if not p.requires_grad)
+            print(f"frozen {tuple(self.exp.freeze)}: {n} of {sum(1 for _ in m.parameters())} parameter tensors",
+                  flush=True)
 
     def resume_train(self, model):
         """trainer.py:312-345.  --resume: model, optimizer, best AP and epoch (and, under --fp16, the
